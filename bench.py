@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Benchmark of the CrossNorm/SelfNorm hot path on MI355X.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 \
         --master-port P bench.py --gpus N --steps K --warmup W
 
@@ -18,18 +18,29 @@ over RCCL each step like DDP would.  `value` = all ranks' algorithmic bytes (8*E
 launch it just joins the group.  With more ranks than devices (a 1-GPU box) the ranks share a device and the
 collectives go over gloo — RCCL refuses two ranks on one device — which still exercises the launcher end to end.
 
-One JSON line is printed by rank 0; it also carries
+A plain run sets up, runs W warm-up steps and K timed steps, and prints one JSON line from rank 0 (`ms_per_step` = the
+wall time of the K timed steps / K).  It carries
   roofline     — the backward launch (dominant kernel) timed with HIP events on the launch stream, priced on the
                  bytes that launch HAS to move (single touch: 3*E*b) against the 8 TB/s peak; the same interval
-                 priced on SURVEY §8(d3)'s two-pass byte count and the in-process copy / triad ceilings ride along
+                 priced on SURVEY §8(d3)'s two-pass byte count rides along
+  arena        — y and dx come from the library's output arena (cnsn_amd.arena: blocks of its own, a stable home; a NEW block
+                 is the fastest of 4 candidates timed when it is created — during the warm-up here).  `ms_per_step` is that default.
+
+`--dump-outputs DIR` writes what the timed path handed its caller in the last timed step (y, dx, the parameter gradients,
+SelfNorm's running statistics) as DIR/<name>.npy in float32 / float64: the inputs are seeded, so two builds can be compared
+output for output (see `dump_outputs`).
+
+`--full` adds everything that is not the headline (each of it also switched off by its own --no-* option):
+  ceiling      — in-process copy / triad and resident-order plane copy ceilings (tools/pattern_bench), before the warm-up
+  alternatives — the same K steps re-timed in the same process with the arena off (`ms_per_step_plain_allocator`: torch's
+                 caching allocator places y and dx).  MI355X's memory has regions that take plane-strided writes 15-20 %
+                 faster (profiles/r04_memory_map.md): `--prospect N` lets the arena time N more candidate blocks and keep the
+                 fastest (cnsn_arena_prospect) and adds `ms_per_step_prospected` — an explicit, bounded search
+  traffic      — live PMC bytes per launch from rocprofv3 passes of this command run as child processes
+  extra        — other modes, dtypes and shapes of the op (crop boxes, bf16, residual block, inference, roofline_bf16) and
+                 the ResNet-50 / FCN-ResNet50 model lines (child processes)
   cpu_baseline — the CPU oracle (a port of the reference's eager PyTorch path) timed on this
                  host's cores on a bounded slice of the same workload (rank 0, N=1 only), plus one thread
-  arena        — y and dx come from the library's output arena (cnsn_amd.arena: blocks of its own, a stable home; a NEW block
-                 is the fastest of 4 candidates timed when it is created — during the warm-up here).  `ms_per_step` is that default; `ms_per_step_plain_allocator` is the same
-                 K steps re-timed in the same process with the arena off (torch's caching allocator places y and dx).
-                 MI355X's memory has regions that take plane-strided writes 15-20 % faster (profiles/r04_memory_map.md):
-                 `--prospect N` lets the arena time N more candidate blocks and keep the fastest (cnsn_arena_prospect) and
-                 adds `ms_per_step_prospected` — an explicit, bounded search that is OFF in the default line
 """
 import argparse
 import json
@@ -58,16 +69,22 @@ def parse():
     ap.add_argument("--crop", type=str, default="neither", choices=["neither", "style", "content", "both"])
     ap.add_argument("--kind", type=str, default="cnsn", choices=["cnsn", "cn", "sn"])
     ap.add_argument("--strategy", type=str, default="auto", choices=["auto", "two_pass", "resident", "local"])
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-extra", action="store_true", help="skip the secondary workloads (crop=both, bf16)")
-    ap.add_argument("--no-ceiling", action="store_true", help="skip the copy / triad / access-order ceilings (child runs)")
+    ap.add_argument("--full", action="store_true",
+                    help="measure everything besides the headline too: ceilings, the other allocator, live PMC traffic, other "
+                         "modes / dtypes / shapes, model lines, CPU baseline (minutes; each can be left out by its --no-* option)")
+    ap.add_argument("--dump-outputs", type=str, default=None, metavar="DIR",
+                    help="after the timed steps, write what the last timed step computed as DIR/<name>.npy (headline workload)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline")
+    ap.add_argument("--no-extra", action="store_true",
+                    help="with --full: skip the live traffic passes and the secondary workloads (crop=both, bf16, model lines)")
+    ap.add_argument("--no-ceiling", action="store_true", help="with --full: skip the copy / triad / access-order ceilings")
     ap.add_argument("--no-arena", action="store_true", help="y / dx from torch's caching allocator (cnsn_amd.arena off)")
     ap.add_argument("--prospect", type=int, default=0,
-                    help="let the output arena time this many candidate blocks of the input's size and keep the 4 fastest "
-                         "(cnsn_arena_prospect); adds ms_per_step_prospected to the line (never the headline).  0: no search")
+                    help="with --full: let the output arena time this many candidate blocks of the input's size and keep the 4 "
+                         "fastest (cnsn_arena_prospect); adds ms_per_step_prospected to the line (never the headline).  0: no search")
     ap.add_argument("--no-alt", action="store_true",
-                    help="only the contract's W + K steps: no second window with the other allocator, no prospecting (rocprofv3 "
-                         "passes: the kernel averages then belong to ONE placement)")
+                    help="with --full: only the contract's W + K steps: no second window with the other allocator, no "
+                         "prospecting (rocprofv3 passes: the kernel averages then belong to ONE placement)")
     ap.add_argument("--workload", type=str, default="cnsn", choices=["cnsn", "resnet50", "resnet50_jsd", "wrn40", "seg"],
                     help="cnsn: the fused op at the north-star shape (headline); resnet50 / wrn40: whole "
                          "training steps of the caller backbones (images/s)")
@@ -84,7 +101,37 @@ def parse():
                          "ResNet-50 workloads since round 5 (4 057 -> 5 408 img/s, profiles/r05_nhwc.md)")
     ap.add_argument("--nchw", action="store_true", help="ResNet-50 workloads in torch's default NCHW order (what rounds 1-4 measured)")
     ap.add_argument("--sweep", action="store_true", help="print the SURVEY d1 shape sweep as a markdown table and exit")
-    return ap.parse_args()
+    args = ap.parse_args()
+    if args.prospect > 0 and not args.full:
+        ap.error("--prospect times extra windows: it needs --full")
+    if args.dump_outputs is not None and (args.sweep or args.workload != "cnsn"):
+        ap.error("--dump-outputs writes the headline workload's outputs (--workload cnsn, no --sweep)")
+    return args
+
+
+DUMP_SAMPLE = 1 << 22            # --dump-outputs: elements kept of a larger output (16 MiB as float32)
+DUMP_BUDGET = 64 * 1000 * 1000   # bytes of all dumped files together
+
+
+def dump_outputs(directory, arrays):
+    """Write `arrays` ({name: tensor}) as DIR/<name>.npy, float64 tensors as float64 and everything else as float32.  A tensor
+    of more than DUMP_SAMPLE elements is written as a 1-D sample: the same DUMP_SAMPLE flat indices (logical NCHW order, drawn
+    with a fixed seed and sorted) for every tensor of that size and in every run, so that two runs with the same arguments
+    can be compared element for element."""
+    import numpy as np
+    os.makedirs(directory, exist_ok=True)
+    total = 0
+    for name, t in arrays.items():
+        t = t.detach()
+        if t.numel() > DUMP_SAMPLE:
+            g = torch.Generator().manual_seed(0)
+            idx = torch.randint(0, t.numel(), (DUMP_SAMPLE,), generator=g).sort().values
+            t = t.reshape(-1)[idx.to(t.device)]
+        a = t.to(torch.float64 if t.dtype == torch.float64 else torch.float32).cpu().numpy()
+        total += a.nbytes
+        assert total <= DUMP_BUDGET, f"--dump-outputs: over {DUMP_BUDGET} bytes at {name}"
+        np.save(os.path.join(directory, name + ".npy"), a)
+    return total
 
 
 def conditioned(shape, device, dtype, seed):
@@ -853,6 +900,8 @@ def main():
     ev = {i: [torch.cuda.Event(enable_timing=True) for _ in range(3)] for i in range(0, args.steps, ev_every)}
 
     fault = FaultPlan(rank)
+    last = {}                                         # --dump-outputs: y of the last timed step (dx, grads stay on their tensors)
+    keep_at = args.steps - 1 if args.dump_outputs is not None else -1
 
     def step(i=None):
         fault.before_step()
@@ -872,6 +921,8 @@ def main():
             rec[2].record()
         if dist is not None and params:               # DDP-style gradient all-reduce (RCCL over xGMI)
             dp.allreduce_gradients(params)
+        if i == keep_at:
+            last["y"] = y
 
     # A cluster launch that gave up (the GPU was shared with something that kept part of a persistent grid off the device
     # for seconds) has marked its outputs with NaNs and bumped the library's counter.  Nothing is raised in the middle of a
@@ -915,16 +966,16 @@ def main():
             state.restore()
         raise cnsn_amd.CnsnError("bench: cluster launches still time out after three windows")
 
-    # The box's own ceilings (roofline.ceiling) are measured BEFORE the warm-up: 0.3 s of plain copies in this process.  They
-    # belong to the line either way; ahead of the timed region they also take the device out of its idle clocks — a fresh
-    # process needs ~25 headline steps to settle (profiles/r04_launches_per_step.md: 0.852 ms at steps 5-9, 0.79 from step 25),
-    # more than the W = 5 the driver passes.  W warm-up steps and exactly K timed steps follow as the contract says.
-    ceil = copy_triad_ceiling(dev) if (world == 1 and not args.no_ceiling) else None
+    # With --full the box's own ceilings (roofline.ceiling) are measured BEFORE the warm-up: 0.3 s of plain copies in this
+    # process.  Ahead of the timed region they also take the device out of its idle clocks — a fresh process needs ~25
+    # headline steps to settle (profiles/r04_launches_per_step.md: 0.852 ms at steps 5-9, 0.79 from step 25).  W warm-up steps
+    # and exactly K timed steps follow as the contract says.
+    ceil = copy_triad_ceiling(dev) if (args.full and world == 1 and not args.no_ceiling) else None
     # Where y and dx live.  Default: the library's output arena (cnsn_amd.arena) — blocks of its own, nothing probed, nothing
-    # timed.  --no-arena: torch's caching allocator.  After the contract's W + K steps the same K steps are timed again with
-    # the OTHER allocator (one warm-up window in front) so that the line carries both; --prospect N adds a third window
-    # after the arena has looked at N candidate blocks (profiles/r04_memory_map.md: where a block lies physically decides how
-    # fast the launches write it).
+    # timed.  --no-arena: torch's caching allocator.  With --full, after the contract's W + K steps the same K steps are timed
+    # again with the OTHER allocator (one warm-up window in front) so that the line carries both; --prospect N adds a third
+    # window after the arena has looked at N candidate blocks (profiles/r04_memory_map.md: where a block lies physically
+    # decides how fast the launches write it).
     from cnsn_amd import arena as _arena
     if args.no_arena:
         _arena.disable()
@@ -935,10 +986,18 @@ def main():
         dist.all_reduce(tt, op=dist.ReduceOp.MAX)
         dt = float(tt.item())
     per_rank_timeouts = dp.gather_ints(local_timeouts, dev)
+    if args.dump_outputs is not None and rank == 0:
+        outs = {"y": last.pop("y"), "dx": x.grad}
+        outs.update({"grad_" + k.replace(".", "_"): p.grad for k, p in mod.named_parameters() if p.grad is not None})
+        outs.update({"buffer_" + k.replace(".", "_"): t for k, t in mod.named_buffers() if t.is_floating_point()})
+        nbytes = dump_outputs(args.dump_outputs, outs)
+        print(f"[bench] {len(outs)} outputs of the last timed step ({nbytes / 1e6:.1f} MB) -> {args.dump_outputs}",
+              file=sys.stderr, flush=True)
+    last.clear()
 
     # ---- the same K steps with the other allocator / after a bounded search (outside the contract's timed region)
     alt = {}
-    if world == 1 and cnsn_amd._ffi.glue() is not None and not args.no_alt:
+    if args.full and world == 1 and cnsn_amd._ffi.glue() is not None and not args.no_alt:
         arena_stats = _arena.stats(dev) if not args.no_arena else None
         if args.no_arena:
             _arena.enable()
@@ -1033,7 +1092,7 @@ def main():
                                      "frac": round(need_f / fwd_s / 1e9 / HBM_PEAK_GBS, 4),
                                      "survey_d3_frac": round(3 * e * b / fwd_s / 1e9 / HBM_PEAK_GBS, 4)}},
         }
-        if world == 1 and not args.no_extra:
+        if args.full and world == 1 and not args.no_extra:
             live, why = live_traffic(args)
             if live is not None:
                 out["roofline"]["traffic"], out["roofline"]["traffic_source"] = live["bwd"], why
@@ -1064,7 +1123,7 @@ def main():
                     out["roofline"]["achieved"] / ceil["resident_order_triad_GBps"], 4)
                 out["roofline"]["forward"]["frac_of_resident_order_ceiling"] = round(
                     out["roofline"]["forward"]["achieved"] / ceil["resident_order_copy_GBps"], 4)
-        if world == 1 and not args.no_extra:
+        if args.full and world == 1 and not args.no_extra:
             out["extra"] = secondary_workloads(cnsn_amd, shape, dev, args)
             out["extra"]["residual_block_add_cnsn_relu"] = residual_block_workloads(cnsn_amd, shape, dev)
             out["extra"]["inference"] = inference_workloads(cnsn_amd, shape, dev)
@@ -1074,7 +1133,7 @@ def main():
             out["extra"]["seg_bs16_512"] = {"bf16": model_line("seg", 5, 2, 150, ("--dtype", "bf16")),
                                                "f32_note": "fp32: 102-106 img/s (`--workload seg`, profiles/r05h_seg_f32.json); left out of the "
                                                            "default line to keep it within minutes (a child process per model line)"}
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full and world == 1 and not args.no_cpu_baseline:
             out["cpu_baseline"] = cpu_baseline(shape, args.crop, args.kind, args.cpu_seconds)
         print(json.dumps(out), flush=True)
     if dist is not None:

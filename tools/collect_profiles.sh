@@ -31,7 +31,7 @@ stats resnet50_step python $R/bench.py --workload resnet50 --steps 12 --warmup 4
 cd $R
 timeout 200 tools/pattern_bench 256 256 > $OUT/pattern_bench.txt 2>&1
 timeout 600 python bench.py --sweep > $OUT/shape_sweep.md 2> /dev/null
-timeout 600 python bench.py --steps 50 --warmup 10 > $OUT/bench_n1.json 2> $OUT/bench_n1.err
+timeout 600 python bench.py --steps 50 --warmup 10 --full > $OUT/bench_n1.json 2> $OUT/bench_n1.err
 timeout 600 python bench.py --steps 20 --warmup 5 > $OUT/bench_driver_style.json 2> $OUT/bench_driver_style.err
 for w in resnet50 resnet50_jsd wrn40 seg; do timeout 300 python bench.py --workload $w --steps 30 --warmup 8 2>/dev/null | tail -1 >> $OUT/model_workloads.jsonl; done
 timeout 300 python bench.py --workload wrn40 --steps 60 --warmup 15 --no-graph 2>/dev/null | tail -1 >> $OUT/model_workloads.jsonl
