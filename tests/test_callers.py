@@ -106,6 +106,58 @@ def test_resnet50_logits_match_reference_on_gpu(g6):
     assert float((rv - torch.from_numpy(g6["r50_f64_rv_last"])).abs().max()) < 1e-3
 
 
+@pytest.mark.gpu
+@pytest.mark.skipif(not torch.cuda.is_available(), reason="needs an MI355X")
+def test_resnet50_train_step_channels_last_matches_reference_gradients(g6, golden_dir):
+    """G6b: one training step of the ResNet-50 caller in channels-last — every bottleneck tail in the fused launch — against the
+    imported reference's step in fp64 (gen_golden_models_grad.py): logits, running statistics and the layer-4 / fc gradients
+    by value at the G6 bar; the stem's and the layer-1 gate's gradients by direction (53 MIOpen convolutions and 49 ReLUs
+    between them and the loss, test_gpu_nhwc.py::test_resnet50_in_channels_last_matches_the_nchw_model)."""
+    import cnsn_amd
+    g6b = np.load(os.path.join(golden_dir, "g6b_r50_grad.npz"))
+    m = make_r50(cnsn_amd.cnsn).cuda().to(memory_format=torch.channels_last).train()
+    x = torch.from_numpy(g6["r50_x"]).cuda().contiguous(memory_format=torch.channels_last)
+    logits = m(x)
+    # all 16 bottleneck tails took the fused launch (N = 4: every site's plan is fused)
+    seen, todo, fused = set(), [logits.grad_fn], 0
+    while todo:
+        fn = todo.pop()
+        if fn is None or fn in seen:
+            continue
+        seen.add(fn)
+        fused += type(fn).__name__ == "FusedBnBlockBackward"
+        todo.extend(nxt for nxt, _ in fn.next_functions)
+    assert fused == 16, fused
+    (logits * torch.from_numpy(g6b["w"]).float().cuda()).sum().backward()
+    torch.cuda.synchronize()
+
+    def bar(name, got, t64, t32, tol=1e-3):
+        t64, t32 = torch.from_numpy(t64), torch.from_numpy(t32).double()
+        got = got.detach().cpu().double().reshape(t64.shape)
+        err, ref_err, scale = float((got - t64).abs().max()), float((t32 - t64).abs().max()), float(t64.abs().max())
+        assert err <= max(tol * scale, 3 * ref_err), f"{name}: err {err:.3e}, reference fp32 err {ref_err:.3e}, scale {scale:.3g}"
+
+    def cos(name, got, t64, t32):
+        # cosine distance <= max(1e-3, 3 x the reference's own fp32 distance) — the G6 bar's construction: the reference's fp32
+        # step itself is at 1 - 1.4e-3 (layer-1 gate, conv1) from its fp64 step
+        v = torch.from_numpy(t64).flatten()
+        d = [1 - float(torch.nn.functional.cosine_similarity(u.double().flatten(), v, dim=0))
+             for u in (got.detach().cpu(), torch.from_numpy(t32))]
+        assert d[0] <= max(1e-3, 3 * d[1]), f"{name}: cosine distance {d[0]:.2e}, reference fp32 {d[1]:.2e}"
+
+    bar("logits", logits, g6b["f64_logits"], g6b["f32_logits"])
+    params, state = dict(m.named_parameters()), m.state_dict()
+    for k in [str(v) for v in g6b["running_names"]]:
+        bar(k, state[k], g6b[f"f64_{k}"], g6b[f"f32_{k}"])
+    rows = int(g6b["fc_rows"])
+    for k in [str(v) for v in g6b["grad_names"]]:
+        got = params[k].grad[:rows] if k == "fc.weight" else params[k].grad
+        if k.startswith(("layer4.", "fc.")):
+            bar(f"grad {k}", got, g6b[f"f64_grad_{k}"], g6b[f"f32_grad_{k}"])
+        else:
+            cos(f"grad {k}", got, g6b[f"f64_grad_{k}"], g6b[f"f32_grad_{k}"])
+
+
 def test_jsd_properties_and_steps_on_cpu():
     from oracle import jsd_oracle
     torch.manual_seed(0)
