@@ -14,7 +14,7 @@ STRATEGY_AUTO, STRATEGY_TWO_PASS, STRATEGY_RESIDENT, STRATEGY_LOCAL, STRATEGY_MO
 ADD_NONE, ADD_PRE, ADD_POST = 0, 1, 2
 LAYOUT_NCHW, LAYOUT_NHWC = 0, 1
 PATHS = {0: "streaming", 1: "packed", 2: "resident", 3: "local", 4: "mono"}
-ABI_VERSION = 8
+ABI_VERSION = 9
 PERM_INLINE_MAX = 1024       # CNSN_PERM_INLINE_MAX
 E_UNSUPPORTED = -9
 
@@ -50,6 +50,14 @@ class BnTail(C.Structure):
     _fields_ = [("struct_bytes", C.c_int32), ("training", C.c_int32), ("eps", C.c_float), ("momentum", C.c_float),
                 ("weight", C.c_void_p), ("bias", C.c_void_p), ("running_mean", C.c_void_p), ("running_var", C.c_void_p),
                 ("num_batches_tracked", C.c_void_p)]
+
+
+class Ibn(C.Structure):
+    """cnsn_ibn_t (ABI 9)"""
+    _fields_ = [("struct_bytes", C.c_int32), ("dtype", C.c_int32), ("N", C.c_int32), ("C", C.c_int32), ("H", C.c_int32),
+                ("W", C.c_int32), ("half", C.c_int32), ("relu", C.c_int32), ("eps_in", C.c_float), ("reserved", C.c_int32),
+                ("in_weight", C.c_void_p), ("in_bias", C.c_void_p), ("bn", BnTail), ("context", C.c_void_p),
+                ("context_bytes", C.c_uint64)]
 
 
 class ArenaStats(C.Structure):
@@ -127,6 +135,13 @@ SIGNATURES = {
     "cnsn_backward_bnrelu": (C.c_int, [C.POINTER(Problem), C.POINTER(Epilogue), C.POINTER(BnTail), C.c_void_p, C.c_void_p,
                                        C.c_void_p, C.POINTER(Gate), C.c_void_p, C.c_void_p, C.c_void_p,
                                        C.POINTER(GateGrad), C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]),
+    "cnsn_ibn_plan": (C.c_int, [C.POINTER(Ibn), C.c_int, C.c_int]),
+    "cnsn_ibn_saved_floats": (C.c_size_t, [C.POINTER(Ibn)]),
+    "cnsn_ibn_workspace_bytes": (C.c_size_t, [C.POINTER(Ibn)]),
+    "cnsn_forward_ibn": (C.c_int, [C.POINTER(Ibn), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t,
+                                   C.c_void_p]),
+    "cnsn_backward_ibn": (C.c_int, [C.POINTER(Ibn), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                    C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]),
     "cnsn_jsd_workspace_bytes": (C.c_size_t, [C.c_int]),
     "cnsn_jsd": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p,
                            C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]),

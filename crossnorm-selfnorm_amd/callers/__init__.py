@@ -5,10 +5,11 @@ structure (random CrossNorm site activation, 3-view JSD consistency).  Stock `nn
 `nn.BatchNorm2d` (MIOpen) everywhere else: only the CNSN path is this repository's own kernels."""
 from .ibn import IBN, InstanceNorm2d
 from .resnet import ResNet50CNSN
+from .resnet_ibn import ResNet50IBNCNSN, resnet50_ibn_a, resnet50_ibn_b
 from .segmentation import FCNHead, SegResNet50CNSN, poly_learning_rate
 from .steps import (GraphedIdleStep, StepGuard, image_space_crossnorm, jsd_consistency, train_step_cn, train_step_cn_consistency,
                     train_step_image_cn_views)
 from .wideresnet import WideResNetCNSN
 
-__all__ = ["WideResNetCNSN", "ResNet50CNSN", "SegResNet50CNSN", "FCNHead", "poly_learning_rate", "IBN", "InstanceNorm2d", "jsd_consistency", "train_step_cn", "train_step_cn_consistency",
+__all__ = ["WideResNetCNSN", "ResNet50CNSN", "ResNet50IBNCNSN", "resnet50_ibn_a", "resnet50_ibn_b", "SegResNet50CNSN", "FCNHead", "poly_learning_rate", "IBN", "InstanceNorm2d", "jsd_consistency", "train_step_cn", "train_step_cn_consistency",
            "image_space_crossnorm", "train_step_image_cn_views", "GraphedIdleStep", "StepGuard"]

@@ -9,22 +9,28 @@ import torch.nn as nn
 
 from . import _sites
 from ._sites import CrossNormSites, make_cnsn, residual_sum
+from .ibn import IBN, InstanceNorm2d
 
 
 class _Bottleneck(nn.Module):
     expansion = 4
 
-    def __init__(self, impl, c_in, planes, stride, downsample, pos, beta, crop, cnsn_type):
+    def __init__(self, impl, c_in, planes, stride, downsample, pos, beta, crop, cnsn_type, ibn=None):
         super().__init__()
         c_out = planes * self.expansion
+        self.ibn = ibn                                 # the IBN-Net variant of callers/resnet_ibn.py (resnet_ibn_cnsn.py:49-87)
         self.conv1 = nn.Conv2d(c_in, planes, 1, bias=False)
-        self.bn1 = nn.BatchNorm2d(planes)
+        self.bn1 = IBN(planes) if ibn == "a" else nn.BatchNorm2d(planes)
         self.conv2 = nn.Conv2d(planes, planes, 3, stride, 1, bias=False)
         self.bn2 = nn.BatchNorm2d(planes)
         self.conv3 = nn.Conv2d(planes, c_out, 1, bias=False)
         self.bn3 = nn.BatchNorm2d(c_out)
+        if ibn == "b":                                 # :63 — registered where the reference registers it (state_dict order)
+            self.IN = InstanceNorm2d(c_out, affine=True)
         self.relu = nn.ReLU(inplace=True)
         self.downsample = downsample
+        if ibn == "b" and pos == "post":               # the InstanceNorm2d takes the unit's place (:66-67)
+            cnsn_type = None
         if cnsn_type is not None:                      # None: CrossNorm only in image space (:62)
             assert pos in ("residual", "pre", "post", "identity")
             self.cnsn = make_cnsn(impl, cnsn_type, crop, beta, c_in if pos == "pre" else c_out)   # :73-80
@@ -32,9 +38,18 @@ class _Bottleneck(nn.Module):
 
     def forward(self, x):
         h = self.cnsn(x) if self.pos == "pre" else x
-        h = self.relu(self.bn1(self.conv1(h)))
+        h = self.conv1(h)
+        h = self.bn1.forward_act(h) if self.ibn == "a" else self.relu(self.bn1(h))   # IBN + ReLU: one launch on channels-last
         h = self.relu(self.bn2(self.conv2(h)))
         h = self.conv3(h)
+        if self.ibn == "b":                            # resnet_ibn_cnsn.py:108-122: relu(IN(bn3(h) + identity))
+            skip = x if self.downsample is None else self.downsample(x)
+            h = self.bn3(h)
+            if self.pos == "residual":
+                h = self.cnsn(h)
+            elif self.pos == "identity":
+                skip = self.cnsn(skip)
+            return self.IN.forward_act(h, skip, relu=True)
         # :99-122.  pos='post': bn3 (and the downsample's BatchNorm2d), the add, the CNSN unit and the ReLU are ONE call when the
         # unit offers it (this library's `CNSN.forward_bn_block`: one launch per direction on channels-last tensors, the
         # un-fused sequence otherwise)

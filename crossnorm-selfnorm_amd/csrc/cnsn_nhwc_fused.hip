@@ -2,95 +2,13 @@
 #include "cnsn_nhwc.h"
 
 #include "cnsn_nhwc_bnhead_kernels.h"
+#include "cnsn_nhwc_fused_host.h"
 #include "cnsn_nhwc_fused_kernels.h"
 #include "cnsn_resident_host.h"
 
 namespace cnsn {
 
-namespace {
-
-int vec_of(int dtype) { return 16 / elem_bytes(dtype); }
-size_t align256(size_t v) { return (v + 255) & ~(size_t)255; }
-
-// 0 never, 1 the AUTO rule (default), 2 wherever the kernels apply, n > 2: AUTO for tensors of at most n MiB (CNSN_NHWC_FUSED)
-int fused_mode() {
-    const char* e = knob(K_NHWC_FUSED);
-    if (!e) return 1;
-    const int v = atoi(e);
-    return v < 0 ? 0 : v;
-}
-
-template <typename F>
-bool dispatch_t(int dtype, F&& f) {
-    if (dtype == CNSN_F32) {
-        f(TypeTag<float>{}, IntTag<4>{});
-        return true;
-    }
-    if (dtype == CNSN_BF16) {
-        f(TypeTag<bf16_t>{}, IntTag<8>{});
-        return true;
-    }
-    if (dtype == CNSN_F16) {
-        f(TypeTag<_Float16>{}, IntTag<8>{});
-        return true;
-    }
-    return false;
-}
-
-template <typename F>
-void with_add(int add, F&& f) {
-    if (add == ADD_PRE)
-        f(IntTag<ADD_PRE>{});
-    else if (add == ADD_POST)
-        f(IntTag<ADD_POST>{});
-    else
-        f(IntTag<ADD_NONE>{});
-}
-
-NhwcFusedArgs make_args(const Plan& pl, const NhwcGeom& ng, int relu, int gc) {
-    const cnsn_problem_t& p = pl.pr;
-    NhwcFusedArgs a{};
-    a.g = ng;
-    a.ntiles = ng.N * ng.S * ng.ncb;
-    a.ngroups = p.C / gc;
-    a.training = p.sn_training ? 1 : 0;
-    a.relu = relu;
-    a.keep = 0;
-    a.eps_sn = p.eps_sn;
-    a.eps_bn = p.eps_bn;
-    a.momentum = p.momentum;
-    a.inv_n = pl.mid.inv_n;
-    a.unbias_n = pl.mid.unbias_n;
-    a.bar.host_flag = resident_host_flag();
-    a.bar.wait_ticks = resident_wait_ticks();
-    const char* fi = knob(K_FAULT_INJECT);
-    a.bar.fault = (fi && fi[0] == '1') ? 1 : 0;
-    a.bar.ctl_idle = 0u;
-    return a;
-}
-
-// issue `kern` with a co-resident grid (a multiple of 8: the barrier's groups are equal); the barriers are booked on the
-// context before the launch.  `a`: the kernel's first argument (NhwcFusedArgs, or a struct that holds one), `fa` the
-// NhwcFusedArgs inside it
-template <typename A, typename Kern, typename... Args>
-int launch_fused(const Plan& pl, Kern kern, size_t lds, A& a, NhwcFusedArgs& fa, void* ws_bar, hipStream_t stream, Args... args) {
-    const int grid = reshost::grid_for(kern, lds, 8, fa.ntiles & ~7);
-    if (grid < 8) return CNSN_E_UNSUPPORTED;
-    ResidentChain chain(stream);  // persistent grids of different streams never overlap
-    const BarArea ba = resident_bar_area(pl.pr, ws_bar, stream, grid, 2);
-    if (ba.need_fill) {
-        const hipError_t e = hipMemsetAsync(ws_bar, 0, kBarBlock, stream);
-        if (e != hipSuccess) return (int)e;
-    }
-    fa.bar.ctl = ba.ctl;
-    fa.bar.block = ba.block;
-    fa.bar.group_base = ba.group_base;
-    fa.bar.bar_base = ba.bar_base;
-    kern<<<grid, kBlock, lds, stream>>>(a, args...);
-    return launch_status();
-}
-
-}  // namespace
+using namespace nhwc_host;
 
 NhwcGeom nhwc_fused_geom(const Plan& pl) {
     const cnsn_problem_t& p = pl.pr;

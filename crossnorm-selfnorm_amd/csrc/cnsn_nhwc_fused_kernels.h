@@ -198,21 +198,13 @@ __device__ __forceinline__ void store_group(float* __restrict__ p, const float (
 // ================================================================================================
 // forward
 // ================================================================================================
-// SUM (ADD_PRE only): phase A also writes X = x + addend to a.sum_out (default cache policy), phase C reads that ONE tensor;
-// the backward is then the ADD_NONE backward on X (cnsn_epilogue_t.sum_out, ABI 8)
-template <typename T, int VEC, int ADD, bool KEEP, bool SUM = false>
-__global__ __launch_bounds__(kBlock, CNSN_NHWC_WG_PER_CU) void nhwc_fused_fwd_kernel(NhwcFusedArgs a, const T* __restrict__ x,
-                                                                                      const T* __restrict__ addend, T* __restrict__ y,
-                                                                                      GateDev gg) {
-    static_assert(!SUM || ADD == ADD_PRE, "the kept sum is the PRE add's");
-    T* const xsum = SUM ? (T*)a.sum_out : nullptr;  // (written in phase A, read in phase C: no __restrict__)
-    extern __shared__ float lds[];
-    __shared__ double red[4 * CNSN_NHWC_GC];
-    __shared__ int bar_flag;
-    constexpr int GC = CNSN_NHWC_GC;
+// Phase A of the forward (every single-launch forward runs it): each workgroup walks its tiles (instance, pixel chunk, column
+// block) and writes the column sums of X = x [+ addend] about the plane's first pixel as partial moments [chunk][2][plane]
+// (a.part, write-through) and that shift (a.kshift); SUM: X is also written to xsum
+template <typename T, int VEC, int ADD, bool KEEP, bool SUM>
+__device__ __forceinline__ void nhwc_fwd_phase_a(const NhwcFusedArgs& a, const T* __restrict__ x, const T* __restrict__ addend, T* xsum,
+                                                 float* lds) {
     const NhwcGeom& g = a.g;
-
-    // ---- A: partial moments of every tile
     for (int tile = blockIdx.x; tile < a.ntiles; tile += gridDim.x) {
         const NhwcThread<VEC> t(g, tile);
         float K[VEC], acc[2][VEC];
@@ -262,6 +254,24 @@ __global__ __launch_bounds__(kBlock, CNSN_NHWC_WG_PER_CU) void nhwc_fused_fwd_ke
         nhwc_rows_sum<VEC, 2, true>(g, t, acc, lds, a.part);
         __syncthreads();  // (lds is the next tile's)
     }
+}
+
+// SUM (ADD_PRE only): phase A also writes X = x + addend to a.sum_out (default cache policy), phase C reads that ONE tensor;
+// the backward is then the ADD_NONE backward on X (cnsn_epilogue_t.sum_out, ABI 8)
+template <typename T, int VEC, int ADD, bool KEEP, bool SUM = false>
+__global__ __launch_bounds__(kBlock, CNSN_NHWC_WG_PER_CU) void nhwc_fused_fwd_kernel(NhwcFusedArgs a, const T* __restrict__ x,
+                                                                                      const T* __restrict__ addend, T* __restrict__ y,
+                                                                                      GateDev gg) {
+    static_assert(!SUM || ADD == ADD_PRE, "the kept sum is the PRE add's");
+    T* const xsum = SUM ? (T*)a.sum_out : nullptr;  // (written in phase A, read in phase C: no __restrict__)
+    extern __shared__ float lds[];
+    __shared__ double red[4 * CNSN_NHWC_GC];
+    __shared__ int bar_flag;
+    constexpr int GC = CNSN_NHWC_GC;
+    const NhwcGeom& g = a.g;
+
+    // ---- A: partial moments of every tile
+    nhwc_fwd_phase_a<T, VEC, ADD, KEEP, SUM>(a, x, addend, xsum, lds);
     if (!grid_barrier(a.bar, 1, &bar_flag)) {
         nhwc_mark_owed<T, VEC>(g, a.ntiles, y);
         return;
@@ -602,7 +612,7 @@ __global__ __launch_bounds__(kBlock, CNSN_NHWC_WG_PER_CU) void nhwc_fused_bwd_ke
 // the SLIM record for the two-pass channels-last kernels (cnsn_nhwc.hip): they compute with the common record of cnsn_layout.h
 // in their workspace; these two kernels move between the records, so that any forward feeds any backward
 // ================================================================================================
-__global__ __launch_bounds__(kBlock) void nhwc_slim_from_saved_kernel(const double* __restrict__ saved, int N, int C,
+static __global__ __launch_bounds__(kBlock) void nhwc_slim_from_saved_kernel(const double* __restrict__ saved, int N, int C,
                                                                       float* __restrict__ slim) {
     const size_t P = (size_t)N * C, p = (size_t)blockIdx.x * kBlock + threadIdx.x;
     if (p < (size_t)C) slim_rstd(slim, P)[p] = saved[(size_t)SV_ROWS * P + p];
@@ -619,7 +629,7 @@ __global__ __launch_bounds__(kBlock) void nhwc_slim_from_saved_kernel(const doub
 
 // ... and back: the rows a SelfNorm-only backward reads (cnsn_mid_kernels.h::mid_bwd_a_kernel, load_cn_rows' constants for the
 // rest) + the plane-order float rows of the channels-last tensor passes ([0] float(mean), [1..3] a_in = g, xr = 0, b_in = 0)
-__global__ __launch_bounds__(kBlock) void nhwc_saved_from_slim_kernel(const float* __restrict__ slim, int N, int C, int relu,
+static __global__ __launch_bounds__(kBlock) void nhwc_saved_from_slim_kernel(const float* __restrict__ slim, int N, int C, int relu,
                                                                       double* __restrict__ saved, float* __restrict__ rows) {
     const size_t P = (size_t)N * C, p = (size_t)blockIdx.x * kBlock + threadIdx.x;
     if (p < (size_t)C) {

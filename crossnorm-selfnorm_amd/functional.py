@@ -983,6 +983,129 @@ class InstanceNorm(torch.autograd.Function):
         return dx, dweight, dbias, None
 
 
+# ------------------------------------------------------------------------------------------------
+# Instance-Batch normalisation on channels-last tensors: y = act(Norm(x [+ addend])), InstanceNorm2d on channels [0, half),
+# BatchNorm2d on the rest, ONE launch per direction (cnsn_forward_ibn / cnsn_backward_ibn, csrc/cnsn_nhwc_ibn_kernels.h)
+# ------------------------------------------------------------------------------------------------
+_ibn_plan_cache = {}
+_ffi._plan_caches.append(_ibn_plan_cache)
+
+
+def _ibn_desc(x: torch.Tensor, half: int, relu: bool, eps_in: float, in_w=None, in_b=None, bn: Optional[_ffi.BnTail] = None):
+    n, c, h, w = _dims(x)
+    d = _ffi.Ibn()
+    d.struct_bytes = C.sizeof(_ffi.Ibn)
+    d.dtype, d.N, d.C, d.H, d.W = _DTYPES[x.dtype], n, c, h, w
+    d.half, d.relu, d.eps_in = int(half), int(bool(relu)), float(eps_in)
+    d.in_weight, d.in_bias = (in_w.data_ptr() if in_w is not None else None), (in_b.data_ptr() if in_b is not None else None)
+    if bn is not None:
+        d.bn = bn
+    elif half < c:
+        d.bn.struct_bytes = C.sizeof(_ffi.BnTail)
+    return d
+
+
+def ibn_plan(x: torch.Tensor, half: int, relu: bool = True, has_addend: bool = False, bn_training: bool = True) -> bool:
+    """True when ONE launch per direction evaluates `act(IBN(x [+ addend]))` for this tensor (cnsn_ibn_plan, both directions:
+    channels-last, fp32 / bf16 / f16, C and half multiples of 8, 2 <= N <= 256, H*W >= 2, no unforgiven time-out, CNSN_NHWC_FUSED
+    not 0) — and never while the stream is being captured into a graph (as `bn_block_plan`).  Remembered per (shape, dtype,
+    configuration)."""
+    if not x.is_cuda or x.dim() != 4 or x.dtype not in _DTYPES or torch.cuda.is_current_stream_capturing():
+        return False
+    if not x.is_contiguous(memory_format=torch.channels_last) or x.is_contiguous():
+        return False
+    if _ffi.lib().cnsn_resident_degraded():      # (a persistent launch gave up and nobody re-armed since: today's path)
+        return False
+    key = (tuple(x.shape), x.dtype, x.device.index, int(half), bool(relu), bool(has_addend), bool(bn_training))
+    hit = _ibn_plan_cache.get(key)
+    if hit is None:
+        d = _ibn_desc(x, half, relu, 1e-5)
+        d.bn.training = int(bool(bn_training))
+        lib = _ffi.lib()
+        hit = lib.cnsn_ibn_plan(C.byref(d), int(has_addend), 0) == 1 and lib.cnsn_ibn_plan(C.byref(d), int(has_addend), 1) == 1
+        _ibn_plan_cache[key] = hit
+    return hit
+
+
+class IBNorm(torch.autograd.Function):
+    """y = act(Norm(x [+ addend])) on a channels-last tensor: nn.InstanceNorm2d (biased variance + eps_in, optional affine) on
+    channels [0, half), nn.BatchNorm2d (training: batch statistics and the running-buffer update in the launch; eval: running
+    statistics) on [half, C) — the IBN layer of models/imagenet/resnet_ibn_cnsn.py:24-44 (half == C: the IBN-b InstanceNorm2d,
+    :65,:117-121) and the ReLU behind it.  3 tensor passes forward, 5 backward (+ 2 each way for the addend); saves x (and the
+    addend) and five floats per plane, never y.  The caller resolves BatchNorm2d's per-call book-keeping (`momentum=None`,
+    `num_batches_tracked`: SelfNorm._bn_call_state)."""
+
+    @staticmethod
+    def forward(ctx, x, addend, in_w, in_b, bn_w, bn_b, bn_rm, bn_rv, half, relu, eps_in, bn_training, bn_eps, bn_momentum,
+                bn_nbt=None):
+        _require_device(x, "cnsn_forward_ibn")
+        with torch.cuda.device(x.device):
+            lib = _ffi.lib()
+            _ffi.check_resident_health("cnsn_forward_ibn")
+            x = _dense_cl(x)
+            if addend is not None:
+                _require_device(addend, "cnsn_forward_ibn(addend)")
+                assert addend.shape == x.shape and addend.dtype == x.dtype, "addend must match x"
+                addend = _dense_cl(addend)
+            dev = x.device
+            n, c = int(x.shape[0]), int(x.shape[1])
+            iw = _f32(in_w) if in_w is not None else None
+            ib = _f32(in_b) if in_b is not None else None
+            bn, bw, bb = None, None, None
+            if half < c:
+                bw, bb = _f32(bn_w), _f32(bn_b)
+                bn = _ffi.BnTail(C.sizeof(_ffi.BnTail), int(bool(bn_training)), float(bn_eps), float(bn_momentum), bw.data_ptr(),
+                                 bb.data_ptr(), bn_rm.data_ptr(), bn_rv.data_ptr(), _ptr(bn_nbt))
+            d = _ibn_desc(x, half, relu, eps_in, iw, ib, bn)
+            prob = _problem(x, FusedConfig(sn_active=True))      # (the persistent context of the single-launch kernels)
+            prob.layout = _ffi.LAYOUT_NHWC
+            _context(prob, dev)
+            d.context, d.context_bytes = prob.context, prob.context_bytes
+            need_bwd = any(ctx.needs_input_grad)
+            saved = torch.empty(lib.cnsn_ibn_saved_floats(C.byref(d)), dtype=torch.float32, device=dev) if need_bwd else None
+            ws_bytes = lib.cnsn_ibn_workspace_bytes(C.byref(d))
+            ws = torch.empty(ws_bytes // 4 + 4, dtype=torch.float32, device=dev)
+            y = _out_like(x)
+            st = lib.cnsn_forward_ibn(C.byref(d), _ptr(x), _ptr(addend), _ptr(y), _ptr(saved), _ptr(ws), ws_bytes, _stream(x))
+            _ffi.check(st, "cnsn_forward_ibn")
+            if need_bwd:
+                ctx.desc, ctx.prob, ctx.keep = d, prob, (iw, ib, bw, bb)   # (the descriptor points at them)
+                ctx.has_addend = addend is not None
+                ctx.param_dtypes = tuple(t.dtype if t is not None else None for t in (in_w, in_b, bn_w, bn_b))
+                ctx.save_for_backward(x, addend, saved)
+            return y
+
+    @staticmethod
+    def backward(ctx, gy):
+        x, addend, saved = ctx.saved_tensors
+        with torch.cuda.device(x.device):
+            lib = _ffi.lib()
+            d = ctx.desc
+            dev = x.device
+            c, half = int(x.shape[1]), int(d.half)
+            gy = _dense_cl(gy if gy.dtype == x.dtype else gy.to(x.dtype))
+            prob = ctx.prob
+            _context(prob, dev)                                  # (the context in force now, as the other backwards take it)
+            d.context, d.context_bytes = prob.context, prob.context_bytes
+            if torch.cuda.is_current_stream_capturing():
+                d.context, d.context_bytes = None, 0
+            dx = _out_like(x)
+            flat = torch.empty(2 * c, dtype=torch.float32, device=dev)
+            diw, dib, dbw, dbb = flat[:half], flat[half:2 * half], flat[2 * half:c + half], flat[c + half:]
+            pd = ctx.param_dtypes
+            ws_bytes = lib.cnsn_ibn_workspace_bytes(C.byref(d))
+            ws = torch.empty(ws_bytes // 4 + 4, dtype=torch.float32, device=dev)
+            st = lib.cnsn_backward_ibn(C.byref(d), _ptr(gy), _ptr(x), _ptr(addend), _ptr(saved), _ptr(dx),
+                                       _ptr(diw) if pd[0] is not None else None, _ptr(dib) if pd[1] is not None else None,
+                                       _ptr(dbw) if pd[2] is not None else None, _ptr(dbb) if pd[3] is not None else None,
+                                       _ptr(ws), ws_bytes, _stream(x))
+            _ffi.check(st, "cnsn_backward_ibn")           # (never declines the record of its own forward: cnsn_nhwc_ibn.hip)
+            grads = [None if pd[i] is None else (t if t.dtype == pd[i] else t.to(pd[i])) for i, t in enumerate((diw, dib, dbw, dbb))]
+            #       x   addend                          in_w      in_b      bn_w      bn_b      rm    rv    half  relu  eps   tr    eps   mom   nbt
+            return (dx, dx if ctx.has_addend else None, grads[0], grads[1], grads[2], grads[3], None, None, None, None, None, None, None,
+                    None, None)
+
+
 class JsdConsistency(torch.autograd.Function):
     """Jensen-Shannon consistency of three (B, K) logit tensors — cnsn_jsd: loss and gradient in one launch
     (reference imagenet.py:367-381, cifar.py:173-186)."""

@@ -43,7 +43,7 @@
 extern "C" {
 #endif
 
-#define CNSN_ABI_VERSION 8
+#define CNSN_ABI_VERSION 9
 
 /* Largest batch whose permutation can travel as a launch argument (cnsn_problem_t.perm_host). */
 #define CNSN_PERM_INLINE_MAX 1024
@@ -345,6 +345,58 @@ int cnsn_backward_bn_block(const cnsn_problem_t* prob, const cnsn_epilogue_t* ep
                            const float* saved, const float* bn_stats, void* grad_conv_out, void* grad_identity,
                            const cnsn_gate_grad_t* dg, float* d_bn_weight, float* d_bn_bias, float* d_bn_skip_weight,
                            float* d_bn_skip_bias, void* workspace, size_t workspace_bytes, void* stream);
+
+/* ---- Instance-Batch normalisation on channels-last tensors (round 7, ABI 9) -----------------------------------------------
+ * The IBN layers of the reference's ResNet-50-IBN-a/b (models/imagenet/resnet_ibn_cnsn.py:24-44: `IBN` = nn.InstanceNorm2d on
+ * channels [0, half) and nn.BatchNorm2d on [half, C), torch.split + torch.cat, :63; nn.InstanceNorm2d(affine=True) on every
+ * channel at the IBN-b stem and block ends, :65,:117-121,:138-139), each followed by the block's ReLU.  These entry points
+ * evaluate
+ *       y = act( Norm( x [+ addend] ) ),   act = ReLU or the identity,
+ * with Norm = InstanceNorm2d (per (n, c) plane: mean, BIASED variance + eps_in, optional affine) on channels c < half and
+ * BatchNorm2d (per channel over N, H, W; training: batch statistics, running_mean / running_var (unbiased) updated with
+ * `momentum`, num_batches_tracked += 1 — momentum=None is resolved by the caller as nn.BatchNorm2d does; eval: the running
+ * statistics) on the rest, in ONE persistent launch per direction (csrc/cnsn_nhwc_ibn_kernels.h).  Tensor passes: forward 3
+ * (x read twice, y written once), backward 5 (grad_y and x twice, grad_x once); an addend adds two reads each way.  The
+ * backward recomputes the ReLU mask from x and `saved` with the forward's own expression (it equals y > 0; y is never read).
+ *   - channels-last layout; fp32 / bf16 / f16 activations, fp32 parameters; C a whole number of 16-byte vectors and of 8;
+ *     half a positive multiple of 8 (half == C: InstanceNorm2d alone; plain BatchNorm2d, half == 0, is not offered);
+ *     2 <= N <= 256; H*W >= 2; no unforgiven time-out (cnsn_resident_degraded); the co-resident kernels allowed
+ *     (cnsn_resident_enable(0) / CNSN_RESIDENT=0 switch these launches off too, as the other single launches); CNSN_NHWC_FUSED
+ *     not 0 and, above 2, the tensor of at most that many MiB.  cnsn_ibn_plan()
+ *     answers this as a pure function of the call; an ineligible call returns CNSN_E_UNSUPPORTED and launches nothing.  The
+ *     BACKWARD of a forward these kernels ran is always taken (health and switches are not asked again).
+ *   - `saved`: cnsn_ibn_saved_floats() floats — five per plane in plane order (p = n*C + c): the apply coefficients a, xr, b
+ *     (y = act(a*(X - xr) + b)), the plane's 1/std r (a BatchNorm2d channel's in each of its planes) and mean - xr.  The forward
+ *     writes it (may be NULL when no backward follows), the backward reads it with the same descriptor.
+ *   - workspace: cnsn_ibn_workspace_bytes() (either direction).  context: as cnsn_problem_t.context (cnsn_context_init).
+ *   - backward: grad_x is the gradient of x and, with an addend, of the addend too (the caller aliases it); d_in_weight /
+ *     d_in_bias (half) and d_bn_weight / d_bn_bias (C - half) are written, not accumulated; any of them may be NULL.  A launch
+ *     that gives up marks what it still owed with NaNs (outputs and parameter gradients), as the library's other launches do. */
+typedef struct cnsn_ibn {
+    int32_t struct_bytes;   /* = sizeof(cnsn_ibn_t)                                                        */
+    int32_t dtype;          /* enum cnsn_dtype of x / addend / y / grad tensors (channels-last)           */
+    int32_t N, C, H, W;
+    int32_t half;           /* channels [0, half): InstanceNorm2d; [half, C): BatchNorm2d                  */
+    int32_t relu;           /* 1: y = max(y, 0) last                                                      */
+    float eps_in;           /* InstanceNorm2d eps, 1e-5                                                   */
+    int32_t reserved;
+    const float* in_weight; /* (half) or NULL (affine=False)                                              */
+    const float* in_bias;   /* (half) or NULL                                                             */
+    cnsn_bn_tail_t bn;      /* BatchNorm2d of channels [half, C): arrays of C - half; ignored when half == C */
+    void* context;          /* persistent context (cnsn_context_init) or NULL                             */
+    uint64_t context_bytes;
+} cnsn_ibn_t;
+
+/* 1 when the single launch takes the call (has_addend: x + addend is normalised; backward: the backward's answer), 0 when
+ * not, < 0 argument error */
+int cnsn_ibn_plan(const cnsn_ibn_t* desc, int has_addend, int backward);
+size_t cnsn_ibn_saved_floats(const cnsn_ibn_t* desc);
+size_t cnsn_ibn_workspace_bytes(const cnsn_ibn_t* desc);
+int cnsn_forward_ibn(const cnsn_ibn_t* desc, const void* x, const void* addend, void* y, float* saved, void* workspace,
+                     size_t workspace_bytes, void* stream);
+int cnsn_backward_ibn(const cnsn_ibn_t* desc, const void* grad_y, const void* x, const void* addend, const float* saved,
+                      void* grad_x, float* d_in_weight, float* d_in_bias, float* d_bn_weight, float* d_bn_bias, void* workspace,
+                      size_t workspace_bytes, void* stream);
 
 /* ---- persistent exchange context of the cluster-resident strategy --------------------------------
  * The resident kernels hand per-plane scalars from workgroup to workgroup through device memory.  Through the
