@@ -60,6 +60,13 @@ class Ibn(C.Structure):
                 ("context_bytes", C.c_uint64)]
 
 
+class BnAct(C.Structure):
+    """cnsn_bn_act_t (ABI 9, added in round 8)"""
+    _fields_ = [("struct_bytes", C.c_int32), ("dtype", C.c_int32), ("N", C.c_int32), ("C", C.c_int32), ("H", C.c_int32),
+                ("W", C.c_int32), ("relu", C.c_int32), ("add", C.c_int32), ("bn", BnTail), ("context", C.c_void_p),
+                ("context_bytes", C.c_uint64)]
+
+
 class ArenaStats(C.Structure):
     """cnsn_arena_stats_t"""
     _fields_ = [("struct_bytes", C.c_int32), ("device", C.c_int32), ("chunk_bytes", C.c_uint64), ("mapped_bytes", C.c_uint64),
@@ -142,6 +149,13 @@ SIGNATURES = {
                                    C.c_void_p]),
     "cnsn_backward_ibn": (C.c_int, [C.POINTER(Ibn), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
                                     C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]),
+    "cnsn_bn_act_plan": (C.c_int, [C.POINTER(BnAct), C.c_int, C.c_int]),
+    "cnsn_bn_act_saved_floats": (C.c_size_t, [C.POINTER(BnAct)]),
+    "cnsn_bn_act_workspace_bytes": (C.c_size_t, [C.POINTER(BnAct)]),
+    "cnsn_forward_bn_act": (C.c_int, [C.POINTER(BnAct), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t,
+                                      C.c_void_p]),
+    "cnsn_backward_bn_act": (C.c_int, [C.POINTER(BnAct), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                       C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]),
     "cnsn_jsd_workspace_bytes": (C.c_size_t, [C.c_int]),
     "cnsn_jsd": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p,
                            C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]),

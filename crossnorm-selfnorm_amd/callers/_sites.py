@@ -11,6 +11,9 @@ FUSE_BLOCK = os.environ.get("CNSN_FUSE_BLOCK", "1") != "0"
 # WideResNet: also hand the NEXT block's relu(bn1(.)) out of the op's launch (CNSN.forward_block_bn, cnsn_forward_bnrelu;
 # SURVEY §8 f1, second half).  CNSN_FUSE_TAIL=0 keeps bn1 / relu1 as separate ops.
 FUSE_TAIL = FUSE_BLOCK and os.environ.get("CNSN_FUSE_TAIL", "1") != "0"
+# `relu(bn(x))` and the plain block end `relu(bn3(h) + skip)` through this library's single launch on channels-last tensors
+# (callers/bn_act.py, cnsn_forward_bn_act).  CNSN_BN_ACT=0 (or setting this to False) keeps nn.BatchNorm2d and the ReLU.
+FUSE_BN_ACT = os.environ.get("CNSN_BN_ACT", "1") != "0"
 
 
 def residual_sum(cnsn, pos, residual, skip, relu, skip_first=False):

@@ -9,6 +9,7 @@ import torch.nn as nn
 
 from . import _sites
 from ._sites import CrossNormSites, make_cnsn, residual_sum
+from .bn_act import bn_act
 from .ibn import IBN, InstanceNorm2d
 
 
@@ -39,8 +40,9 @@ class _Bottleneck(nn.Module):
     def forward(self, x):
         h = self.cnsn(x) if self.pos == "pre" else x
         h = self.conv1(h)
-        h = self.bn1.forward_act(h) if self.ibn == "a" else self.relu(self.bn1(h))   # IBN + ReLU: one launch on channels-last
-        h = self.relu(self.bn2(self.conv2(h)))
+        # BatchNorm2d (IBN) + ReLU: one launch on channels-last tensors (callers/bn_act.py, IBN.forward_act)
+        h = self.bn1.forward_act(h) if self.ibn == "a" else bn_act(self.bn1, h)
+        h = bn_act(self.bn2, self.conv2(h))
         h = self.conv3(h)
         if self.ibn == "b":                            # resnet_ibn_cnsn.py:108-122: relu(IN(bn3(h) + identity))
             skip = x if self.downsample is None else self.downsample(x)
@@ -61,7 +63,9 @@ class _Bottleneck(nn.Module):
                 return fb(h, self.bn3, self.downsample[0](x), relu=True, identity_bn=self.downsample[1])
             return fb(h, self.bn3, self.downsample(x), relu=True)
         skip = x if self.downsample is None else self.downsample(x)
-        return residual_sum(getattr(self, "cnsn", None), self.pos, self.bn3(h), skip, relu=True)
+        if getattr(self, "cnsn", None) is None:        # no unit here: the plain end relu(bn3(h) + skip)
+            return bn_act(self.bn3, h, skip)
+        return residual_sum(self.cnsn, self.pos, self.bn3(h), skip, relu=True)
 
 
 class ResNet50CNSN(nn.Module, CrossNormSites):
@@ -99,6 +103,6 @@ class ResNet50CNSN(nn.Module, CrossNormSites):
     def forward(self, x, aug=False):
         if aug:
             self._enable_cross_norm()
-        x = self.maxpool(self.relu(self.bn1(self.conv1(x))))
+        x = self.maxpool(bn_act(self.bn1, self.conv1(x)))
         x = self.layer4(self.layer3(self.layer2(self.layer1(x))))
         return self.fc(torch.flatten(self.avgpool(x), 1))

@@ -13,6 +13,7 @@ import torch
 import torch.nn as nn
 
 from ._sites import CrossNormSites
+from .bn_act import bn_act
 from .ibn import InstanceNorm2d
 from .resnet import _Bottleneck
 
@@ -55,7 +56,7 @@ class ResNet50IBNCNSN(nn.Module, CrossNormSites):
         if aug:
             self._enable_cross_norm()
         x = self.conv1(x)
-        x = self.bn1.forward_act(x) if isinstance(self.bn1, InstanceNorm2d) else self.relu(self.bn1(x))
+        x = self.bn1.forward_act(x) if isinstance(self.bn1, InstanceNorm2d) else bn_act(self.bn1, x)
         x = self.maxpool(x)
         x = self.layer4(self.layer3(self.layer2(self.layer1(x))))
         return self.fc(torch.flatten(self.avgpool(x), 1))

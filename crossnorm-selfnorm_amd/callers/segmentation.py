@@ -13,6 +13,7 @@ import torch
 import torch.nn as nn
 
 from ._sites import residual_sum
+from .bn_act import bn_act
 
 
 class _SegBottleneck(nn.Module):
@@ -44,16 +45,18 @@ class _SegBottleneck(nn.Module):
 
     def forward(self, x):
         h = self.cnsn(x) if (self.custom and self.pos == "pre") else x
-        h = self.relu(self.bn1(self.conv1(h)))
-        h = self.relu(self.bn2(self.conv2(h)))
-        h = self.bn3(self.conv3(h))
+        h = bn_act(self.bn1, self.conv1(h))                                  # BatchNorm2d + ReLU: one launch on channels-last
+        h = bn_act(self.bn2, self.conv2(h))
+        h = self.conv3(h)
         skip = x if self.downsample is None else self.downsample(x)
         if self.custom and self.pos == "residual":
-            out = residual_sum(self.cnsn, "residual", h, skip, relu=True)   # cnsn(out); out += identity; relu  (:296-303)
-        else:
-            if self.custom and self.pos == "identity":
-                skip = self.cnsn(h)                                          # (sic, :298-299: applied to `out`)
+            out = residual_sum(self.cnsn, "residual", self.bn3(h), skip, relu=True)   # cnsn(out); out += identity; relu  (:296-303)
+        elif self.custom and self.pos == "identity":
+            h = self.bn3(h)
+            skip = self.cnsn(h)                                              # (sic, :298-299: applied to `out`)
             out = torch.relu(h + skip)
+        else:
+            out = bn_act(self.bn3, h, skip)                                  # the plain end relu(bn3(h) + skip)
         if self.custom:
             if self.pos == "post":
                 out = self.cnsn(out)                                         # after the ReLU here (:304-305)
@@ -127,7 +130,7 @@ class SegResNet50CNSN(nn.Module):
     def forward(self, x, aug=False):                                         # :453-471 (sites are armed by the trainer,
         if 0 in self.block_idxs:                                             #  tool/train_cnsn.py:305-310)
             x = self.img_cn(x)
-        x = self.maxpool(self.relu(self.bn1(self.conv1(x))))
+        x = self.maxpool(bn_act(self.bn1, self.conv1(x)))
         x = self.layer3(self.layer2(self.layer1(x)))
         aux = x
         return {"out": self.layer4(x), "aux": aux}
@@ -140,6 +143,9 @@ class FCNHead(nn.Sequential):
         inter = in_channels // 4
         super().__init__(nn.Conv2d(in_channels, inter, 3, padding=1, bias=False), nn.BatchNorm2d(inter), nn.ReLU(),
                          nn.Dropout(0.1), nn.Conv2d(inter, channels, 1))
+
+    def forward(self, x):                    # (the Sequential's indices, hence its state_dict keys, stay; [2] is the ReLU)
+        return self[4](self[3](bn_act(self[1], self[0](x))))
 
 
 def poly_learning_rate(base_lr, curr_iter, max_iter, power=0.9):

@@ -1,5 +1,5 @@
 // Host helpers of the channels-last single-launch kernels, shared by their translation units (cnsn_nhwc_fused.hip: SelfNorm and the
-// bottleneck tail; cnsn_nhwc_ibn.hip: Instance-Batch normalisation): dtype dispatch, the launch arguments every family starts from,
+// bottleneck tail; cnsn_nhwc_ibn.hip: Instance-Batch normalisation; cnsn_nhwc_bn.hip: BatchNorm2d + ReLU): dtype dispatch, the launch arguments every family starts from,
 // and the co-resident launch with its barrier booking.
 #pragma once
 #include <cstdio>
@@ -77,25 +77,40 @@ inline NhwcFusedArgs make_args(const Plan& pl, const NhwcGeom& ng, int relu, int
     return a;
 }
 
-// issue `kern` with a co-resident grid (a multiple of 8: the barrier's groups are equal); the barriers are booked on the
-// context before the launch.  `a`: the kernel's first argument (NhwcFusedArgs, or a struct that holds one), `fa` the
-// NhwcFusedArgs inside it
+// issue `kern` with a co-resident grid (a multiple of 8: the barrier's groups are equal) of at most `ntiles` workgroups; the two
+// barriers are booked on the context before the launch.  `a`: the kernel's first argument, `bar` the GridBar inside it
 template <typename A, typename Kern, typename... Args>
-int launch_fused(const Plan& pl, Kern kern, size_t lds, A& a, NhwcFusedArgs& fa, void* ws_bar, hipStream_t stream, Args... args) {
-    const int grid = reshost::grid_for(kern, lds, 8, fa.ntiles & ~7);
+int launch_coresident(const cnsn_problem_t& pr, Kern kern, size_t lds, A& a, GridBar& bar, int ntiles, void* ws_bar,
+                      hipStream_t stream, Args... args) {
+    const int grid = reshost::grid_for(kern, lds, 8, ntiles & ~7);
     if (grid < 8) return CNSN_E_UNSUPPORTED;
     ResidentChain chain(stream);  // persistent grids of different streams never overlap
-    const BarArea ba = resident_bar_area(pl.pr, ws_bar, stream, grid, 2);
+    const BarArea ba = resident_bar_area(pr, ws_bar, stream, grid, 2);
     if (ba.need_fill) {
         const hipError_t e = hipMemsetAsync(ws_bar, 0, kBarBlock, stream);
         if (e != hipSuccess) return (int)e;
     }
-    fa.bar.ctl = ba.ctl;
-    fa.bar.block = ba.block;
-    fa.bar.group_base = ba.group_base;
-    fa.bar.bar_base = ba.bar_base;
+    bar.ctl = ba.ctl;
+    bar.block = ba.block;
+    bar.group_base = ba.group_base;
+    bar.bar_base = ba.bar_base;
     kern<<<grid, kBlock, lds, stream>>>(a, args...);
     return launch_status();
+}
+
+// ... for the kernels whose first argument is, or holds, a NhwcFusedArgs (`fa`)
+template <typename A, typename Kern, typename... Args>
+int launch_fused(const Plan& pl, Kern kern, size_t lds, A& a, NhwcFusedArgs& fa, void* ws_bar, hipStream_t stream, Args... args) {
+    return launch_coresident(pl.pr, kern, lds, a, fa.bar, fa.ntiles, ws_bar, stream, args...);
+}
+
+// the barrier's host-side fields (bounded wait, give-up protocol, the tests' fault switch)
+inline void init_grid_bar(GridBar& bar) {
+    bar.host_flag = resident_host_flag();
+    bar.wait_ticks = resident_wait_ticks();
+    const char* fi = knob(K_FAULT_INJECT);
+    bar.fault = (fi && fi[0] == '1') ? 1 : 0;
+    bar.ctl_idle = 0u;
 }
 
 }  // namespace nhwc_host

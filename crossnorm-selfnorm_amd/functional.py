@@ -1106,6 +1106,131 @@ class IBNorm(torch.autograd.Function):
                     None, None)
 
 
+# ------------------------------------------------------------------------------------------------
+# BatchNorm2d (+ add) + ReLU on channels-last tensors: y = act(BatchNorm2d(x) [+ addend]), ONE launch per direction in training
+# mode, one plain launch in eval mode (cnsn_forward_bn_act / cnsn_backward_bn_act, csrc/cnsn_nhwc_bn_kernels.h)
+# ------------------------------------------------------------------------------------------------
+_bn_act_plan_cache = {}
+_ffi._plan_caches.append(_bn_act_plan_cache)
+
+
+def _bn_act_desc(x: torch.Tensor, relu: bool, has_addend: bool, bn: Optional[_ffi.BnTail] = None, training: bool = True):
+    n, c, h, w = _dims(x)
+    d = _ffi.BnAct()
+    d.struct_bytes = C.sizeof(_ffi.BnAct)
+    d.dtype, d.N, d.C, d.H, d.W = _DTYPES[x.dtype], n, c, h, w
+    d.relu, d.add = int(bool(relu)), int(bool(has_addend))
+    if bn is not None:
+        d.bn = bn
+    else:
+        d.bn.struct_bytes = C.sizeof(_ffi.BnTail)
+    d.bn.training = int(bool(training))
+    return d
+
+
+def bn_act_plan(x: torch.Tensor, relu: bool = True, has_addend: bool = False, training: bool = True) -> bool:
+    """True when the library's own launch evaluates `act(BatchNorm2d(x) [+ addend])` for this tensor (cnsn_bn_act_plan): a HIP
+    tensor in strict channels-last order, fp32 / bf16 / f16, C a whole number of 16-byte vectors, any N.  Training mode: both
+    directions of the single launch (at least 8 tiles of 64 rows; no unforgiven time-out, `set_resident` / CNSN_RESIDENT and
+    CNSN_NHWC_FUSED as for the other single launches).  Eval mode: the plain forward launch (no backward: the caller keeps
+    today's path when a gradient is needed).  Remembered per (shape, dtype, configuration)."""
+    if not x.is_cuda or x.dim() != 4 or x.dtype not in _DTYPES:
+        return False
+    if not x.is_contiguous(memory_format=torch.channels_last) or x.is_contiguous():
+        return False
+    if training and _ffi.lib().cnsn_resident_degraded():      # (a persistent launch gave up and nobody re-armed since)
+        return False
+    key = (tuple(x.shape), x.dtype, x.device.index, bool(relu), bool(has_addend), bool(training))
+    hit = _bn_act_plan_cache.get(key)
+    if hit is None:
+        d = _bn_act_desc(x, relu, has_addend, training=training)
+        lib = _ffi.lib()
+        hit = lib.cnsn_bn_act_plan(C.byref(d), int(has_addend), 0) == 1
+        if training:
+            hit = hit and lib.cnsn_bn_act_plan(C.byref(d), int(has_addend), 1) == 1
+        _bn_act_plan_cache[key] = hit
+    return hit
+
+
+class BatchNormAct(torch.autograd.Function):
+    """y = act(BatchNorm2d(x) [+ addend]) on a channels-last tensor — `relu(bn(conv(x)))` and the plain block end
+    `relu(bn3(h) + identity)` of the backbones.  Training: batch statistics, the running-buffer update and
+    `num_batches_tracked += 1` inside ONE launch per direction, 3 tensor passes forward (+ 1 for the addend), 5 backward; saves
+    x, the addend when the ReLU follows it, and 2*C floats (mean, rstd) — never y.  Eval: the running statistics, one plain
+    launch, no backward.  The caller resolves BatchNorm2d's per-call book-keeping (`momentum=None`, `num_batches_tracked`:
+    SelfNorm._bn_call_state)."""
+
+    @staticmethod
+    def forward(ctx, x, addend, bn_w, bn_b, bn_rm, bn_rv, relu, training, bn_eps, bn_momentum, bn_nbt=None):
+        _require_device(x, "cnsn_forward_bn_act")
+        with torch.cuda.device(x.device):
+            lib = _ffi.lib()
+            if training:
+                _ffi.check_resident_health("cnsn_forward_bn_act")
+            x = _dense_cl(x)
+            if addend is not None:
+                _require_device(addend, "cnsn_forward_bn_act(addend)")
+                assert addend.shape == x.shape and addend.dtype == x.dtype, "addend must match x"
+                addend = _dense_cl(addend)
+            dev = x.device
+            bn = _Bn2dBuffers(bn_w, bn_b, bn_rm, bn_rv, bn_eps, bn_momentum, bn_nbt if training else None)
+            bn.c.training = int(bool(training))
+            d = _bn_act_desc(x, relu, addend is not None, bn.c, training)
+            need_bwd = bool(training) and any(ctx.needs_input_grad)    # (eval: forward only — callers.bn_act keeps torch's path
+            prob = None                                                #  when a gradient is needed; the output carries none)
+            if training:
+                prob = _problem(x, FusedConfig(sn_active=True))      # (the persistent context of the single-launch kernels)
+                prob.layout = _ffi.LAYOUT_NHWC
+                _context(prob, dev)
+                d.context, d.context_bytes = prob.context, prob.context_bytes
+            saved = torch.empty(lib.cnsn_bn_act_saved_floats(C.byref(d)), dtype=torch.float32, device=dev) if need_bwd else None
+            ws_bytes = lib.cnsn_bn_act_workspace_bytes(C.byref(d))
+            ws = torch.empty(ws_bytes // 4 + 4, dtype=torch.float32, device=dev)
+            y = _out_like(x)
+            st = lib.cnsn_forward_bn_act(C.byref(d), _ptr(x), _ptr(addend), _ptr(y), _ptr(saved), _ptr(ws), ws_bytes, _stream(x))
+            _ffi.check(st, "cnsn_forward_bn_act")
+            if training:
+                bn.write_back()
+            else:
+                ctx.mark_non_differentiable(y)
+            if need_bwd:
+                ctx.desc, ctx.prob, ctx.keep = d, prob, bn           # (the descriptor points at the float32 parameters)
+                ctx.has_addend, ctx.relu = addend is not None, bool(relu)
+                ctx.param_dtypes = (bn_w.dtype, bn_b.dtype)
+                ctx.save_for_backward(x, addend if relu else None, saved)
+            return y
+
+    @staticmethod
+    def backward(ctx, gy):
+        x, addend, saved = ctx.saved_tensors
+        with torch.cuda.device(x.device):
+            lib = _ffi.lib()
+            d = ctx.desc
+            dev = x.device
+            c = int(x.shape[1])
+            gy = _dense_cl(gy if gy.dtype == x.dtype else gy.to(x.dtype))
+            prob = ctx.prob
+            _context(prob, dev)                                  # (the context in force now, as the other backwards take it)
+            d.context, d.context_bytes = prob.context, prob.context_bytes
+            if torch.cuda.is_current_stream_capturing():
+                d.context, d.context_bytes = None, 0
+            dx = _out_like(x)
+            da = _out_like(x) if addend is not None else None    # (ReLU behind the addend: the masked gradient)
+            flat = torch.empty(2 * c, dtype=torch.float32, device=dev)
+            dw, db = flat[:c], flat[c:]
+            ws_bytes = lib.cnsn_bn_act_workspace_bytes(C.byref(d))
+            ws = torch.empty(ws_bytes // 4 + 4, dtype=torch.float32, device=dev)
+            st = lib.cnsn_backward_bn_act(C.byref(d), _ptr(gy), _ptr(x), _ptr(addend), _ptr(saved), _ptr(dx), _ptr(da), _ptr(dw),
+                                          _ptr(db), _ptr(ws), ws_bytes, _stream(x))
+            _ffi.check(st, "cnsn_backward_bn_act")        # (never declines the record of its own forward: cnsn_nhwc_bn.hip)
+            if ctx.has_addend and da is None:
+                da = gy                                          # (no ReLU: the addend's gradient is grad_y itself)
+            pd = ctx.param_dtypes
+            dw, db = (dw if pd[0] == torch.float32 else dw.to(pd[0])), (db if pd[1] == torch.float32 else db.to(pd[1]))
+            #       x   addend                          w   b   rm    rv    relu  train eps   mom   nbt
+            return dx, (da if ctx.has_addend else None), dw, db, None, None, None, None, None, None, None
+
+
 class JsdConsistency(torch.autograd.Function):
     """Jensen-Shannon consistency of three (B, K) logit tensors — cnsn_jsd: loss and gradient in one launch
     (reference imagenet.py:367-381, cifar.py:173-186)."""

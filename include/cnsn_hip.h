@@ -398,6 +398,56 @@ int cnsn_backward_ibn(const cnsn_ibn_t* desc, const void* grad_y, const void* x,
                       void* grad_x, float* d_in_weight, float* d_in_bias, float* d_bn_weight, float* d_bn_bias, void* workspace,
                       size_t workspace_bytes, void* stream);
 
+/* ---- BatchNorm2d (+ add) + ReLU on channels-last tensors (ABI 9, added in round 8: purely additive, the number stays) ---------
+ * The plainest pattern of the backbones, `relu(bn(conv(x)))` (models/imagenet/resnet_cnsn.py:104-110, :257-259) and the plain block
+ * end `relu(bn3(h) + identity)`.  These entry points evaluate
+ *       y = act( BatchNorm2d(x) [+ addend] ),   act = ReLU or the identity,
+ * on the R x C matrix a channels-last tensor is (R = N*H*W) — csrc/cnsn_nhwc_bn_kernels.h:
+ *   training (bn.training = 1): ONE persistent launch per direction.  Batch statistics per channel over N, H, W (sums about the
+ *     tensor's first row, merged in double), the BIASED variance normalises; running_mean / running_var (unbiased) are updated
+ *     with `momentum` and num_batches_tracked += 1 inside the launch (momentum=None is resolved by the caller as nn.BatchNorm2d
+ *     does).  Tensor passes: forward 3 (x read twice, y written once; the addend is read once more), backward 5 (grad_y and x
+ *     twice, grad_x once; with an addend AND ReLU the addend is read twice and grad_addend written).  The backward recomputes
+ *     the ReLU mask from x (and the addend), weight, bias and `saved` with the forward's own expression (it equals y > 0; y is
+ *     never read).  Values are rounded where the un-fused sequence rounds them: BatchNorm2d's output, then the sum.
+ *   eval (bn.training = 0): the running statistics, one plain element-wise launch (no barrier, no context), 2 passes (+ 1 with
+ *     the addend); forward only — cnsn_bn_act_plan(.., backward = 1) answers 0.
+ *   - channels-last layout; fp32 / bf16 / f16 activations, fp32 parameters and statistics; C a whole number of 16-byte vectors;
+ *     2 <= N*H*W < 2^30; NO limit on N (nothing here is per instance).  Training also asks for at least 8 tiles (a tile: 64 rows
+ *     or more of a column block) and, in the forward: no unforgiven time-out (cnsn_resident_degraded), the co-resident kernels
+ *     allowed (cnsn_resident_enable(0) / CNSN_RESIDENT=0 switch these launches off too), CNSN_NHWC_FUSED not 0 and, above 2, the
+ *     tensor of at most that many MiB.  Eval asks for CNSN_NHWC_FUSED not 0 alone.  cnsn_bn_act_plan() answers this as a pure
+ *     function of the call; an ineligible call returns CNSN_E_UNSUPPORTED and launches nothing.  The BACKWARD of a forward these
+ *     kernels ran is always taken (health and switches are not asked again).
+ *   - `saved`: cnsn_bn_act_saved_floats() = 2*C floats — the batch mean (rounded to float, as y was evaluated with it) and rstd
+ *     of every channel: O(C), nothing per plane.  The forward writes it (may be NULL when no backward follows), the backward
+ *     reads it with the same descriptor (weight and bias unchanged in between).
+ *   - workspace: cnsn_bn_act_workspace_bytes() (either direction).  context: as cnsn_problem_t.context (cnsn_context_init).
+ *   - backward: grad_x, d_weight, d_bias (C; either may be NULL) are written, not accumulated.  relu = 1 with an addend:
+ *     grad_addend (the masked grad_y) is written too and must be given; relu = 0: the addend's gradient is grad_y itself —
+ *     addend and grad_addend are ignored.  A launch that gives up marks what it still owed with NaNs (outputs and parameter
+ *     gradients), as the library's other launches do. */
+typedef struct cnsn_bn_act {
+    int32_t struct_bytes;   /* = sizeof(cnsn_bn_act_t)                                                     */
+    int32_t dtype;          /* enum cnsn_dtype of x / addend / y / grad tensors (channels-last)           */
+    int32_t N, C, H, W;
+    int32_t relu;           /* 1: y = max(y, 0) last                                                      */
+    int32_t add;            /* 1: the call carries an addend (informative: the pointer decides)           */
+    cnsn_bn_tail_t bn;      /* the BatchNorm2d: arrays of C                                               */
+    void* context;          /* persistent context (cnsn_context_init) or NULL                             */
+    uint64_t context_bytes;
+} cnsn_bn_act_t;
+
+/* 1 when the launch takes the call (backward: the backward's answer), 0 when not, < 0 argument error */
+int cnsn_bn_act_plan(const cnsn_bn_act_t* desc, int has_addend, int backward);
+size_t cnsn_bn_act_saved_floats(const cnsn_bn_act_t* desc);
+size_t cnsn_bn_act_workspace_bytes(const cnsn_bn_act_t* desc);
+int cnsn_forward_bn_act(const cnsn_bn_act_t* desc, const void* x, const void* addend, void* y, float* saved, void* workspace,
+                        size_t workspace_bytes, void* stream);
+int cnsn_backward_bn_act(const cnsn_bn_act_t* desc, const void* grad_y, const void* x, const void* addend, const float* saved,
+                         void* grad_x, void* grad_addend, float* d_weight, float* d_bias, void* workspace, size_t workspace_bytes,
+                         void* stream);
+
 /* ---- persistent exchange context of the cluster-resident strategy --------------------------------
  * The resident kernels hand per-plane scalars from workgroup to workgroup through device memory.  Through the
  * per-call `workspace` (contents unknown) that memory has to be filled with an 'empty' pattern by a launch of its own
