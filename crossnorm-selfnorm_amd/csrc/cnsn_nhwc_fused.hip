@@ -52,7 +52,8 @@ bool nhwc_fused_ok(const Plan& pl, bool check_health) {
     if (p.N > kBlock || p.C % CNSN_NHWC_GC != 0 || p.H * p.W < 2) return false;  // (phase B: a thread per instance)
     if (check_health && p.strategy == CNSN_STRATEGY_AUTO && !resident_auto_enabled()) return false;
     if (mode > 2 && p.strategy == CNSN_STRATEGY_AUTO && pl.P * (size_t)(p.H * p.W) * elem_bytes(p.dtype) > ((size_t)mode << 20)) return false;
-    return true;
+    const NhwcGeom g = nhwc_fused_geom(pl);
+    return (long)g.N * g.S * g.ncb >= 8;  // (a grid of at least one workgroup per barrier group: launch_coresident declines fewer tiles)
 }
 
 size_t nhwc_fused_extra_bytes(const Plan& pl) {

@@ -3,7 +3,9 @@ nn.InstanceNorm2d / nn.BatchNorm2d in float64 — what the reference's IBN backb
 (models/imagenet/resnet_ibn_cnsn.py:24-44, :63-65) — through the modules of callers/ibn.py: y, dx, d-addend, every parameter
 gradient, the running buffers, num_batches_tracked and momentum=None; toy shapes over the whole matrix (training / eval,
 ReLU on / off, with / without the addend, affine=False, a constant plane) and every ResNet-50-IBN site at N = 256 in the
-variant the backbone runs; the calls the launch does not take give today's results."""
+variant the backbone runs; the calls the launch does not take give today's results.  Every shape that RUNS the launch here has a
+power-of-two channel count: C = 48 is only asked for its plan (test_fallbacks_give_todays_results), never run — the launch at
+channel counts that are no power of two is test_gpu_nhwc_geometry.py's."""
 import numpy as np
 import pytest
 import torch

@@ -28,7 +28,8 @@ SHAPES = [(4, 8, 8, 8),        # one column block, many rows per workgroup
           (5, 64, 28, 28),     # several pixel chunks
           (37, 8, 56, 56),     # the north-star plane, odd batch
           (9, 2048, 7, 7),     # stage-4 site: 512 (fp32) / 256 (16-bit) vector columns -> column blocks
-          (3, 520, 6, 5)]      # a channel count that is no power of two (130 / 65 vector columns)
+          (3, 520, 6, 5)]      # a channel count that is no power of two (130 / 65 vector columns): 6 / 3 tiles, fewer than the single
+                               # launch's 8, so the TWO-PASS kernels only (the single launches: test_gpu_nhwc_geometry.py)
 EPILOGUES = [("pre", True), ("pre", False), ("post", True), ("post", False), ("none", True), ("none", False)]
 
 

@@ -261,6 +261,7 @@ def run_block(shape, dtype, mode, relu, fused, capfd, monkeypatch):
         else:
             one(f"state {k}", hip["st"][k], t64["st"][k], o32["st"][k], param=True, keep=kf)
     del hip, mask
+    return seen     # (the launches' debug lines: test_gpu_nhwc_geometry.py checks their geometry)
 
 
 @pytest.mark.parametrize("strategy", ["2", "0"], ids=["single-launch", "two-pass"])
@@ -387,6 +388,7 @@ def run_bn_block(shape, dtype, two, capfd, monkeypatch, expect_fused=True):
                 ref32u=None if o32u is None else o32u["st"][k])
     del ref, t64, o32, o32u, hip, mask, conv, idt, gy
     free()
+    return seen
 
 
 @pytest.mark.parametrize("two", [False, True], ids=["identity", "downsample"])
