@@ -1,8 +1,66 @@
 // Channels-last two-pass path: host entry points (cnsn_nhwc.hip).  `cnsn_problem_t.layout` = CNSN_LAYOUT_NHWC.
 #pragma once
+#include <type_traits>
+
 #include "cnsn_host_plan.h"
 
 namespace cnsn {
+
+// ---- pure host helpers of every channels-last unit (no kernels here: cnsn_nhwc.hip includes this header alone)
+namespace nhwc_host {
+
+inline int vec_of(int dtype) { return 16 / elem_bytes(dtype); }
+inline size_t align256(size_t v) { return (v + 255) & ~(size_t)255; }
+inline bool aligned16(const void* p) { return ((uintptr_t)p & 15u) == 0; }
+
+template <typename F>
+bool dispatch_t(int dtype, F&& f) {
+    if (dtype == CNSN_F32) return f(TypeTag<float>{}, IntTag<4>{}), true;
+    if (dtype == CNSN_BF16) return f(TypeTag<bf16_t>{}, IntTag<8>{}), true;
+    if (dtype == CNSN_F16) return f(TypeTag<_Float16>{}, IntTag<8>{}), true;
+    return false;
+}
+
+template <typename F>
+void with_add(int add, F&& f) {  // (the kernels' AddMode has the C ABI's values)
+    if (add == CNSN_ADD_PRE)
+        f(IntTag<CNSN_ADD_PRE>{});
+    else if (add == CNSN_ADD_POST)
+        f(IntTag<CNSN_ADD_POST>{});
+    else
+        f(IntTag<CNSN_ADD_NONE>{});
+}
+
+template <typename F>
+void with_flag(bool on, F&& f) {
+    if (on)
+        f(std::true_type{});
+    else
+        f(std::false_type{});
+}
+
+// A caller-owned workspace handed out region by region, each starting on a 256-byte boundary.  On a null base it only counts, so
+// ONE layout function per kernel family is both its size function and its launch path's pointers: the two cannot drift apart
+// (the last region is the barrier block a persistent grid spins on).  bytes(): the regions + the 256 spare bytes the sizes include.
+struct Carver {
+    char* base;
+    size_t used = 0;
+    explicit Carver(void* workspace) : base((char*)workspace) {}
+    template <typename T = float>
+    T* take(size_t bytes) {
+        T* p = base ? (T*)(base + used) : nullptr;
+        used += align256(bytes);
+        return p;
+    }
+    size_t bytes() const { return used + 256; }
+};
+
+// The first read of a single launch keeps the default cache policy when the second one can find it on chip (what phase A reads
+// within reach of the 256 MiB Infinity Cache); non-temporal like every other single-use access beyond that.  `tensors`: how
+// many tensors of `tensor_bytes` the launch has in flight between the two reads.
+inline int keep_first_read(int tensors, size_t tensor_bytes) { return (size_t)tensors * tensor_bytes <= ((size_t)320 << 20) ? 1 : 0; }
+
+}  // namespace nhwc_host
 
 // the un-boxed op on a channels-last tensor whose channel count is a whole number of 16-byte vectors, no channel permutation
 bool nhwc_supported(const Plan& pl, bool has_chan_perm);

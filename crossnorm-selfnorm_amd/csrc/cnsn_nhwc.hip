@@ -5,11 +5,11 @@
 
 namespace cnsn {
 
+using namespace nhwc_host;
+
 namespace {
 
 constexpr int kTargetBlocks = 2048;  // workgroups a launch aims for (256 CUs x 8)
-
-int vec_of(int dtype) { return 16 / elem_bytes(dtype); }
 
 NhwcGeom make_nhwc_geom(const Plan& pl) {
     const cnsn_problem_t& p = pl.pr;
@@ -33,33 +33,13 @@ NhwcGeom make_nhwc_geom(const Plan& pl) {
     return g;
 }
 
-size_t align256(size_t v) { return (v + 255) & ~(size_t)255; }
-
-template <typename F>
-bool dispatch_nhwc(int dtype, F&& f) {
-    if (dtype == CNSN_F32) {
-        f(TypeTag<float>{}, IntTag<4>{});
-        return true;
-    }
-    if (dtype == CNSN_BF16) {
-        f(TypeTag<bf16_t>{}, IntTag<8>{});
-        return true;
-    }
-    if (dtype == CNSN_F16) {
-        f(TypeTag<_Float16>{}, IntTag<8>{});
-        return true;
-    }
-    return false;
-}
-
-template <typename F>
-void with_add3(int add, F&& f) {
-    if (add == ADD_PRE)
-        f(IntTag<ADD_PRE>{});
-    else if (add == ADD_POST)
-        f(IntTag<ADD_POST>{});
-    else
-        f(IntTag<ADD_NONE>{});
+// behind the two-pass workspace: part | kshift (forward) / rows (backward) | the common `saved` record a SelfNorm-only backward
+// expands the slim one into
+struct TwoPassWs { float *part, *rows; double* expanded; size_t bytes; };  // (expanded: slim record only)
+TwoPassWs two_pass_layout(const Plan& pl, const NhwcGeom& g, void* behind) {
+    Carver c(behind);  // (a braced list is evaluated left to right)
+    return {c.take((size_t)g.S * 2 * g.P * 4), c.take(4 * g.P * 4),
+            nhwc_slim_record(pl) ? c.take<double>(saved_doubles_of(pl) * 8) : nullptr, c.bytes()};
 }
 
 }  // namespace
@@ -72,12 +52,7 @@ bool nhwc_supported(const Plan& pl, bool has_chan_perm) {
     return true;
 }
 
-size_t nhwc_extra_bytes(const Plan& pl) {
-    const NhwcGeom g = make_nhwc_geom(pl);
-    // part | kshift (forward) / rows (backward) | the common `saved` record a SelfNorm-only backward expands the slim one into
-    return align256((size_t)g.S * 2 * g.P * 4) + align256(4 * g.P * 4) + (nhwc_slim_record(pl) ? align256(saved_doubles_of(pl) * 8) : 0) +
-           256;
-}
+size_t nhwc_extra_bytes(const Plan& pl) { return two_pass_layout(pl, make_nhwc_geom(pl), nullptr).bytes; }
 
 size_t nhwc_workspace_bytes(const Plan& pl) {
     if (!nhwc_supported(pl, false)) return 0;
@@ -100,19 +75,19 @@ int nhwc_forward(Plan& pl, int add, int relu, const void* x, const void* addend,
         if (st != CNSN_E_UNSUPPORTED) return st;
     }
     const size_t base = align256(workspace_bytes_of(pl));
-    if (workspace_bytes < base + nhwc_extra_bytes(pl)) return CNSN_E_WORKSPACE;
     const NhwcGeom ng = make_nhwc_geom(pl);
+    const TwoPassWs w = two_pass_layout(pl, ng, (char*)workspace + base);
+    if (workspace_bytes < base + w.bytes) return CNSN_E_WORKSPACE;
     const bool slim = nhwc_slim_record(pl);  // `saved` holds the slim record: the mid kernel's own goes to the workspace
     pl.mid.save_coefs = (relu && saved && !slim) ? 1 : 0;
     const size_t P = pl.P;
     double* mom = (double*)workspace;
     double* saved_d = (saved && !slim) ? (double*)saved : mom + 6 * P;
     float* coef = (float*)(mom + 6 * P + saved_doubles_of(pl));
-    float* part = (float*)((char*)workspace + base);
-    float* kshift = (float*)((char*)part + align256((size_t)ng.S * 2 * P * 4));
+    float *part = w.part, *kshift = w.rows;
     const int blocks = ng.N * ng.S * ng.ncb;
     const int pblocks = (int)((P + kBlock - 1) / kBlock);
-    dispatch_nhwc(p.dtype, [&](auto tt, auto vt) {
+    dispatch_t(p.dtype, [&](auto tt, auto vt) {
         using T = typename decltype(tt)::type;
         constexpr int VEC = decltype(vt)::value;
         const size_t lds = (size_t)2 * ng.rows * ng.tcb * VEC * 4;
@@ -128,14 +103,14 @@ int nhwc_forward(Plan& pl, int add, int relu, const void* x, const void* addend,
     launch_mid_fwd(pl, mom, perm, nullptr, g, f, coef, saved_d, stream);
     if (slim && saved) nhwc_slim_from_saved(pl, saved_d, saved, stream);
     ApplyCoef cf{coef + FC_A_IN * P, coef + FC_XR * P, coef + FC_B_IN * P, coef + FC_A_OUT * P, coef + FC_B_OUT * P};
-    dispatch_nhwc(p.dtype, [&](auto tt, auto vt) {
+    dispatch_t(p.dtype, [&](auto tt, auto vt) {
         using T = typename decltype(tt)::type;
         constexpr int VEC = decltype(vt)::value;
         if (add == ADD_PRE && sum_out) {
             nhwc_apply_fwd_kernel<T, VEC, ADD_NONE><<<blocks, kBlock, 0, stream>>>((const T*)sum_out, nullptr, (T*)y, ng, cf, relu);
             return;
         }
-        with_add3(add, [&](auto at) {
+        with_add(add, [&](auto at) {
             constexpr int ADD = decltype(at)::value;
             nhwc_apply_fwd_kernel<T, VEC, ADD><<<blocks, kBlock, 0, stream>>>((const T*)x, (const T*)addend, (T*)y, ng, cf, relu);
         });
@@ -155,16 +130,16 @@ int nhwc_backward(Plan& pl, int add, int relu, const void* gy, const void* x, co
         if (st != CNSN_E_UNSUPPORTED) return st;
     }
     const size_t base = align256(workspace_bytes_of(pl));
-    if (workspace_bytes < base + nhwc_extra_bytes(pl)) return CNSN_E_WORKSPACE;
     const NhwcGeom ng = make_nhwc_geom(pl);
+    const TwoPassWs w = two_pass_layout(pl, ng, (char*)workspace + base);
+    if (workspace_bytes < base + w.bytes) return CNSN_E_WORKSPACE;
     const size_t P = pl.P;
     double* tmp = (double*)workspace;
     float* sums = (float*)(tmp + BT_ROWS * P);
     float* coef = sums + 4 * P;
     const bool slim = nhwc_slim_record(pl);
-    float* part = (float*)((char*)workspace + base);
-    float* rows = (float*)((char*)part + align256((size_t)ng.S * 2 * P * 4));
-    double* expanded = (double*)((char*)rows + align256(4 * P * 4));  // (slim only)
+    float *part = w.part, *rows = w.rows;
+    double* expanded = w.expanded;
     const double* saved_d = slim ? expanded : (const double*)saved;
     const int blocks = ng.N * ng.S * ng.ncb;
     const int pblocks = (int)((P + kBlock - 1) / kBlock);
@@ -174,11 +149,11 @@ int nhwc_backward(Plan& pl, int add, int relu, const void* gy, const void* x, co
         nhwc_saved_from_slim(pl, saved, relu, expanded, rows, stream);
     else
         nhwc_saved_rows_kernel<<<pblocks, kBlock, 0, stream>>>(saved_d, p.N, p.C, relu, rows);
-    dispatch_nhwc(p.dtype, [&](auto tt, auto vt) {
+    dispatch_t(p.dtype, [&](auto tt, auto vt) {
         using T = typename decltype(tt)::type;
         constexpr int VEC = decltype(vt)::value;
         const size_t lds = (size_t)2 * ng.rows * ng.tcb * VEC * 4;
-        with_add3(eff_add, [&](auto at) {
+        with_add(eff_add, [&](auto at) {
             constexpr int ADD = decltype(at)::value;
             nhwc_bwd_reduce_kernel<T, VEC, ADD><<<blocks, kBlock, lds, stream>>>((const T*)gy, (const T*)x, (const T*)addend, ng, rows,
                                                                                  relu, part);
@@ -186,10 +161,10 @@ int nhwc_backward(Plan& pl, int add, int relu, const void* gy, const void* x, co
     });
     nhwc_finish_sums_kernel<<<pblocks, kBlock, 0, stream>>>(part, ng.S, P, sums);
     launch_mid_bwd(pl, sums, saved_d, perm, nullptr, g, f, dg, df, tmp, coef, stream);
-    dispatch_nhwc(p.dtype, [&](auto tt, auto vt) {
+    dispatch_t(p.dtype, [&](auto tt, auto vt) {
         using T = typename decltype(tt)::type;
         constexpr int VEC = decltype(vt)::value;
-        with_add3(eff_add, [&](auto at) {
+        with_add(eff_add, [&](auto at) {
             constexpr int ADD = decltype(at)::value;
             nhwc_apply_bwd_kernel<T, VEC, ADD><<<blocks, kBlock, 0, stream>>>((const T*)gy, (const T*)x, (const T*)addend, (T*)dx,
                                                                                 (T*)d_addend, ng, coef, rows, relu);

@@ -1,8 +1,6 @@
 // Channels-last single-launch BatchNorm2d (+ add) + ReLU (cnsn_nhwc_bn_kernels.h): host side and the C ABI entry points
 // (include/cnsn_hip.h, ABI 9, added in round 8).  The geometry is this family's own (row chunks x column blocks of the R x C
 // matrix); barrier booking and the co-resident launch are those of the other single launches (cnsn_nhwc_fused_host.h).
-#include <type_traits>
-
 #include "../../include/cnsn_hip.h"
 #include "cnsn_nhwc_bn_kernels.h"
 #include "cnsn_nhwc_fused_host.h"
@@ -14,12 +12,8 @@ using namespace nhwc_host;
 namespace {
 
 int bn_act_parse(const cnsn_bn_act_t* d) {
-    if (!d) return CNSN_E_NULL;
-    if (d->struct_bytes != (int32_t)sizeof(cnsn_bn_act_t)) return CNSN_E_STRUCT;
-    if (d->dtype != CNSN_F32 && d->dtype != CNSN_BF16 && d->dtype != CNSN_F16) return CNSN_E_DTYPE;
-    if (d->N <= 0 || d->C <= 0 || d->H <= 0 || d->W <= 0) return CNSN_E_SHAPE;
-    if (d->bn.struct_bytes != (int32_t)sizeof(cnsn_bn_tail_t)) return CNSN_E_STRUCT;
-    return CNSN_OK;
+    const int st = parse_desc_head(d);
+    return st ? st : parse_bn_tail(d->bn);
 }
 
 long long rows_of(const cnsn_bn_act_t& d) { return (long long)d.N * d.H * d.W; }
@@ -69,26 +63,25 @@ bool bn_act_shape_ok(const cnsn_bn_act_t& d) {
 // barrier, so neither health nor the resident switch bear on it — CNSN_NHWC_FUSED=0 still switches it off
 bool bn_act_ok(const cnsn_bn_act_t& d, bool backward) {
     if (!bn_act_shape_ok(d)) return false;
-    const int mode = fused_mode();
     if (!d.bn.training) {
-        if (backward || mode == 0) return false;
+        if (backward || fused_mode() == 0) return false;
         const BnActGeom g = bn_act_geom(d, true);
         return (long long)g.ncb * g.wpc < ((long long)1 << 31);
     }
-    if (!backward) {
-        if (mode == 0 || !resident_auto_enabled()) return false;  // (resident_auto_enabled: switched on and not degraded)
-        if (mode > 2 && tensor_bytes(d) > ((size_t)mode << 20)) return false;
-    }
+    if (!backward && !single_launch_allowed(tensor_bytes(d))) return false;
     const BnActGeom g = bn_act_geom(d);
     if ((long long)g.ncb * g.wpc < 8) return false;  // (a grid of at least one workgroup per barrier group)
     return (size_t)2 * g.wpc * g.C * 4 < ((size_t)1 << 31);
 }
 
 // part [2][wpc][C] | stat / coef [2][C] | barrier block
+struct BnActWs { float *part, *coef; void* bar; size_t bytes; };
+BnActWs bn_act_layout(const BnActGeom& g, void* workspace) {
+    Carver c(workspace);
+    return {c.take((size_t)2 * g.wpc * g.C * 4), c.take((size_t)2 * g.C * 4), c.take<void>(kBarBlock), c.bytes()};
+}
 size_t bn_act_extra_bytes(const cnsn_bn_act_t& d) {
-    if (!d.bn.training) return 256;
-    const BnActGeom g = bn_act_geom(d);
-    return align256((size_t)2 * g.wpc * g.C * 4) + align256((size_t)2 * g.C * 4) + kBarBlock + 256;
+    return d.bn.training ? bn_act_layout(bn_act_geom(d), nullptr).bytes : Carver(nullptr).bytes();  // (eval: no workspace)
 }
 
 cnsn_problem_t context_of(const cnsn_bn_act_t& d) {
@@ -98,31 +91,17 @@ cnsn_problem_t context_of(const cnsn_bn_act_t& d) {
     return p;
 }
 
-BnActArgs make_bn_act_args(const cnsn_bn_act_t& d, const BnActGeom& g, void* workspace) {
+BnActArgs make_bn_act_args(const cnsn_bn_act_t& d, const BnActGeom& g, const BnActWs& w) {
     BnActArgs a{};
     a.g = g;
     a.ntiles = g.ncb * g.wpc;
     a.relu = d.relu ? 1 : 0;
-    a.bn = BnHeadDev{d.bn.weight, d.bn.bias, d.bn.running_mean, d.bn.running_var, (long long*)d.bn.num_batches_tracked, d.bn.eps,
-                     d.bn.momentum};
-    const double R = (double)g.R;
-    a.inv_r = 1.0 / R;
-    a.unbias_r = R > 1.0 ? R / (R - 1.0) : 1.0;
-    a.part = (float*)workspace;
-    a.stat = a.coef = (float*)((char*)workspace + align256((size_t)2 * g.wpc * g.C * 4));
+    a.bn = bn_head_dev(d.bn);
+    set_bn_count(a, (double)g.R);
+    a.part = w.part;
+    a.stat = a.coef = w.coef;
     init_grid_bar(a.bar);
     return a;
-}
-void* bn_act_bar_block(const BnActArgs& a) { return (char*)a.coef + align256((size_t)2 * a.g.C * 4); }
-
-bool aligned16(const void* p) { return ((uintptr_t)p & 15u) == 0; }
-
-template <typename F>
-void with_flag(bool on, F&& f) {
-    if (on)
-        f(std::true_type{});
-    else
-        f(std::false_type{});
 }
 
 int bn_act_forward(const cnsn_bn_act_t& d, const void* x, const void* addend, void* y, float* saved, void* workspace,
@@ -130,7 +109,7 @@ int bn_act_forward(const cnsn_bn_act_t& d, const void* x, const void* addend, vo
     int status = CNSN_E_UNSUPPORTED;
     if (!d.bn.training) {  // the running statistics: one plain launch
         const BnActGeom g = bn_act_geom(d, true);
-        const BnHeadDev bn{d.bn.weight, d.bn.bias, d.bn.running_mean, d.bn.running_var, nullptr, d.bn.eps, d.bn.momentum};
+        const BnHeadDev bn = bn_head_dev(d.bn, false);
         dispatch_t(d.dtype, [&](auto tt, auto vt) {
             using T = typename decltype(tt)::type;
             constexpr int VEC = decltype(vt)::value;
@@ -144,9 +123,10 @@ int bn_act_forward(const cnsn_bn_act_t& d, const void* x, const void* addend, vo
         return status;
     }
     const BnActGeom g = bn_act_geom(d);
-    BnActArgs a = make_bn_act_args(d, g, workspace);
+    const BnActWs w = bn_act_layout(g, workspace);
+    BnActArgs a = make_bn_act_args(d, g, w);
     if (saved) a.stat = saved;  // (written through: the backward's launch reads it like any other memory)
-    a.keep = tensor_bytes(d) <= ((size_t)320 << 20) ? 1 : 0;  // (the addend is read once, in phase C)
+    a.keep = keep_first_read(1, tensor_bytes(d));  // (the addend is read once, in phase C)
     const cnsn_problem_t pr = context_of(d);
     dispatch_t(d.dtype, [&](auto tt, auto vt) {
         using T = typename decltype(tt)::type;
@@ -155,7 +135,7 @@ int bn_act_forward(const cnsn_bn_act_t& d, const void* x, const void* addend, vo
         with_flag(addend != nullptr, [&](auto at) {
             constexpr bool ADD = decltype(at)::value;
             auto go = [&](auto kern) {
-                status = launch_coresident(pr, kern, lds, a, a.bar, a.ntiles, bn_act_bar_block(a), stream, (const T*)x,
+                status = launch_coresident(pr, kern, lds, a, a.bar, a.ntiles, w.bar, stream, (const T*)x,
                                            (const T*)addend, (T*)y);
             };
             a.keep ? go(nhwc_bnact_fwd_kernel<T, VEC, ADD, true>) : go(nhwc_bnact_fwd_kernel<T, VEC, ADD, false>);
@@ -170,12 +150,13 @@ int bn_act_forward(const cnsn_bn_act_t& d, const void* x, const void* addend, vo
 int bn_act_backward(const cnsn_bn_act_t& d, const void* gy, const void* x, const void* addend, const float* saved, void* dx,
                     void* d_addend, float* d_w, float* d_b, void* workspace, hipStream_t stream) {
     const BnActGeom g = bn_act_geom(d);
-    BnActArgs a = make_bn_act_args(d, g, workspace);
+    const BnActWs w = bn_act_layout(g, workspace);
+    BnActArgs a = make_bn_act_args(d, g, w);
     a.saved = saved;
     a.d_w = d_w;
     a.d_b = d_b;
     const bool add = d.relu && addend;  // (without the ReLU the addend's gradient is grad_y itself: nothing to read or write)
-    a.keep = (size_t)(add ? 3 : 2) * tensor_bytes(d) <= ((size_t)320 << 20) ? 1 : 0;
+    a.keep = keep_first_read(add ? 3 : 2, tensor_bytes(d));
     const cnsn_problem_t pr = context_of(d);
     // launch_coresident cannot decline a call bn_act_ok accepts: the grid is occupancy (>= 1: no scratch, 128 VGPRs) x at least
     // 8 compute units, a multiple of 8 and at most the tiles, which are >= 8 here
@@ -187,7 +168,7 @@ int bn_act_backward(const cnsn_bn_act_t& d, const void* gy, const void* x, const
         with_flag(add, [&](auto at) {
             constexpr bool ADD = decltype(at)::value;
             auto go = [&](auto kern) {
-                status = launch_coresident(pr, kern, lds, a, a.bar, a.ntiles, bn_act_bar_block(a), stream, (const T*)gy, (const T*)x,
+                status = launch_coresident(pr, kern, lds, a, a.bar, a.ntiles, w.bar, stream, (const T*)gy, (const T*)x,
                                            (const T*)addend, (T*)dx, (T*)d_addend);
             };
             a.keep ? go(nhwc_bnact_bwd_kernel<T, VEC, ADD, true>) : go(nhwc_bnact_bwd_kernel<T, VEC, ADD, false>);

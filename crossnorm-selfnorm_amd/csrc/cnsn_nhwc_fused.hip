@@ -1,14 +1,26 @@
 // Channels-last single-launch kernels (cnsn_nhwc_fused_kernels.h): host side.
 #include "cnsn_nhwc.h"
 
-#include "cnsn_nhwc_bnhead_kernels.h"
 #include "cnsn_nhwc_fused_host.h"
-#include "cnsn_nhwc_fused_kernels.h"
-#include "cnsn_resident_host.h"
 
 namespace cnsn {
 
 using namespace nhwc_host;
+
+namespace {
+// part [S][2][P] | forward: kshift, gate (without `saved`) / backward: cX, c0 | barrier block
+struct FusedWs { float *part, *side; void* bar; size_t bytes; };
+FusedWs fused_layout(const NhwcGeom& g, void* workspace) {
+    Carver c(workspace);  // (a braced list is evaluated left to right)
+    return {c.take((size_t)g.S * 2 * g.P * 4), c.take(4 * g.P * 4), c.take<void>(kBarBlock), c.bytes()};
+}
+// part [S][kBnFwd][P] | kshift (conv), kshift (identity), gate / cX, c0 | e0, e1 (x 2 with a BatchNorm2d on the skip path) | barrier block
+struct BnHeadWs { float *part, *side, *chan; void* bar; size_t bytes; };
+BnHeadWs bnhead_layout(const NhwcGeom& g, void* workspace) {
+    Carver c(workspace);
+    return {c.take((size_t)g.S * kBnFwd * g.P * 4), c.take(4 * g.P * 4), c.take(4 * (size_t)g.C * 4), c.take<void>(kBarBlock), c.bytes()};
+}
+}  // namespace
 
 NhwcGeom nhwc_fused_geom(const Plan& pl) {
     const cnsn_problem_t& p = pl.pr;
@@ -51,52 +63,40 @@ bool nhwc_fused_ok(const Plan& pl, bool check_health) {
     if (mode == 0) return false;
     if (p.N > kBlock || p.C % CNSN_NHWC_GC != 0 || p.H * p.W < 2) return false;  // (phase B: a thread per instance)
     if (check_health && p.strategy == CNSN_STRATEGY_AUTO && !resident_auto_enabled()) return false;
-    if (mode > 2 && p.strategy == CNSN_STRATEGY_AUTO && pl.P * (size_t)(p.H * p.W) * elem_bytes(p.dtype) > ((size_t)mode << 20)) return false;
+    if (mode > 2 && p.strategy == CNSN_STRATEGY_AUTO && tensor_bytes(pl) > ((size_t)mode << 20)) return false;
     const NhwcGeom g = nhwc_fused_geom(pl);
     return (long)g.N * g.S * g.ncb >= 8;  // (a grid of at least one workgroup per barrier group: launch_coresident declines fewer tiles)
 }
 
-size_t nhwc_fused_extra_bytes(const Plan& pl) {
-    const NhwcGeom g = nhwc_fused_geom(pl);
-    return align256((size_t)g.S * 2 * g.P * 4) + align256(4 * g.P * 4) + kBarBlock + 256;  // part | kshift, gate / cX, c0 | barrier block
-}
+size_t nhwc_fused_extra_bytes(const Plan& pl) { return fused_layout(nhwc_fused_geom(pl), nullptr).bytes; }
 
 int nhwc_fused_forward(Plan& pl, int add, int relu, const void* x, const void* addend, GateDev gg, void* y, float* saved,
                        void* workspace, size_t workspace_bytes, hipStream_t stream, void* sum_out) {
-    const cnsn_problem_t& p = pl.pr;
     if (!nhwc_fused_ok(pl)) return CNSN_E_UNSUPPORTED;
     if (add != ADD_NONE && !addend) return CNSN_E_NULL;
-    if (workspace_bytes < nhwc_fused_extra_bytes(pl)) return CNSN_E_WORKSPACE;
     const NhwcGeom ng = nhwc_fused_geom(pl);
-    const size_t P = pl.P;
+    const FusedWs w = fused_layout(ng, workspace);
+    if (workspace_bytes < w.bytes) return CNSN_E_WORKSPACE;
     NhwcFusedArgs a = make_args(pl, ng, relu, CNSN_NHWC_GC);
-    a.part = (float*)workspace;
-    a.kshift = (float*)((char*)workspace + align256((size_t)ng.S * 2 * P * 4));
+    a.part = w.part;
+    a.kshift = w.side;
     a.slim = saved;
     a.sum_out = add == ADD_PRE ? sum_out : nullptr;
-    a.gout = saved ? saved + (size_t)SL_G * P : a.kshift + P;
-    // the first read with the default cache policy when the second one can find it on chip (what phase A reads within reach of
-    // the 256 MiB Infinity Cache); non-temporal like every other single-use access beyond that
-    a.keep = (size_t)(add == ADD_PRE ? 2 : 1) * P * ng.M * elem_bytes(p.dtype) <= ((size_t)320 << 20) ? 1 : 0;
-    void* ws_bar = (char*)a.kshift + align256(4 * P * 4);
+    a.gout = saved ? saved + (size_t)SL_G * pl.P : a.kshift + pl.P;
+    a.keep = keep_first_read(add == ADD_PRE ? 2 : 1, tensor_bytes(pl));
     int status = CNSN_E_UNSUPPORTED;
-    dispatch_t(p.dtype, [&](auto tt, auto vt) {
+    dispatch_t(pl.pr.dtype, [&](auto tt, auto vt) {
         using T = typename decltype(tt)::type;
         constexpr int VEC = decltype(vt)::value;
         const size_t lds = (size_t)2 * ng.rows * ng.tcb * VEC * 4;
-        if (a.sum_out) {  // (the second read is of what phase A wrote: the first one need not stay in the caches)
-            status = launch_fused(pl, nhwc_fused_fwd_kernel<T, VEC, ADD_PRE, false, true>, lds, a, a, ws_bar, stream, (const T*)x,
-                                  (const T*)addend, (T*)y, gg);
-            return;
-        }
+        auto go = [&](auto kern) {
+            status = launch_fused(pl, kern, lds, a, a, w.bar, stream, (const T*)x, (const T*)addend, (T*)y, gg);
+        };
+        if (a.sum_out)  // (the second read is of what phase A wrote: the first one need not stay in the caches)
+            return go(nhwc_fused_fwd_kernel<T, VEC, ADD_PRE, false, true>);
         with_add(add, [&](auto at) {
             constexpr int ADD = decltype(at)::value;
-            if (a.keep)
-                status = launch_fused(pl, nhwc_fused_fwd_kernel<T, VEC, ADD, true>, lds, a, a, ws_bar, stream, (const T*)x, (const T*)addend,
-                                      (T*)y, gg);
-            else
-                status = launch_fused(pl, nhwc_fused_fwd_kernel<T, VEC, ADD, false>, lds, a, a, ws_bar, stream, (const T*)x,
-                                      (const T*)addend, (T*)y, gg);
+            a.keep ? go(nhwc_fused_fwd_kernel<T, VEC, ADD, true>) : go(nhwc_fused_fwd_kernel<T, VEC, ADD, false>);
         });
     });
     if (knob(K_DEBUG))
@@ -108,36 +108,32 @@ int nhwc_fused_forward(Plan& pl, int add, int relu, const void* x, const void* a
 int nhwc_fused_backward(Plan& pl, int add, int relu, const void* gy, const void* x, const void* addend, GateDev gg,
                         const float* saved, void* dx, void* d_addend, GateGradDev dg, void* workspace, size_t workspace_bytes,
                         hipStream_t stream) {
-    const cnsn_problem_t& p = pl.pr;
     if (!nhwc_fused_ok(pl)) return CNSN_E_UNSUPPORTED;
     if (!saved) return CNSN_E_NULL;
     if (add == ADD_POST && relu && !d_addend) return CNSN_E_NULL;
-    if (workspace_bytes < nhwc_fused_extra_bytes(pl)) return CNSN_E_WORKSPACE;
+    const NhwcGeom ng = nhwc_fused_geom(pl);
+    const FusedWs w = fused_layout(ng, workspace);
+    if (workspace_bytes < w.bytes) return CNSN_E_WORKSPACE;
     // the backward of an epilogue without ReLU and without PRE add is the plain backward
     const int eff_add = (relu || add == ADD_PRE) ? add : ADD_NONE;
     if (eff_add != ADD_NONE && !addend) return CNSN_E_NULL;
-    const NhwcGeom ng = nhwc_fused_geom(pl);
-    const size_t P = pl.P;
     NhwcFusedArgs a = make_args(pl, ng, relu, CNSN_NHWC_GC_BWD);
-    // (G is one more tensor in flight than forward)
-    a.keep = (size_t)(eff_add != ADD_NONE ? 3 : 2) * P * ng.M * elem_bytes(p.dtype) <= ((size_t)320 << 20) ? 1 : 0;
-    a.part = (float*)workspace;
-    a.coefb = (float*)((char*)workspace + align256((size_t)ng.S * 2 * P * 4));
+    a.keep = keep_first_read(eff_add != ADD_NONE ? 3 : 2, tensor_bytes(pl));  // (G is one more tensor in flight than forward)
+    a.part = w.part;
+    a.coefb = w.side;
     a.slim = const_cast<float*>(saved);
-    void* ws_bar = (char*)a.coefb + align256(4 * P * 4);
     int status = CNSN_E_UNSUPPORTED;
-    dispatch_t(p.dtype, [&](auto tt, auto vt) {
+    dispatch_t(pl.pr.dtype, [&](auto tt, auto vt) {
         using T = typename decltype(tt)::type;
         constexpr int VEC = decltype(vt)::value;
         const size_t lds = (size_t)2 * ng.rows * ng.tcb * VEC * 4;
+        auto go = [&](auto kern) {
+            status = launch_fused(pl, kern, lds, a, a, w.bar, stream, (const T*)gy, (const T*)x, (const T*)addend, (T*)dx, (T*)d_addend, gg,
+                                  dg);
+        };
         with_add(eff_add, [&](auto at) {
             constexpr int ADD = decltype(at)::value;
-            if (a.keep)
-                status = launch_fused(pl, nhwc_fused_bwd_kernel<T, VEC, ADD, true>, lds, a, a, ws_bar, stream, (const T*)gy, (const T*)x,
-                                      (const T*)addend, (T*)dx, (T*)d_addend, gg, dg);
-            else
-                status = launch_fused(pl, nhwc_fused_bwd_kernel<T, VEC, ADD, false>, lds, a, a, ws_bar, stream, (const T*)gy, (const T*)x,
-                                      (const T*)addend, (T*)dx, (T*)d_addend, gg, dg);
+            a.keep ? go(nhwc_fused_bwd_kernel<T, VEC, ADD, true>) : go(nhwc_fused_bwd_kernel<T, VEC, ADD, false>);
         });
     });
     if (knob(K_DEBUG))
@@ -169,55 +165,44 @@ bool nhwc_bnhead_ok(const Plan& pl, bool check_health) {
     return (size_t)g.S * kBnFwd * g.P * 4 < ((size_t)1 << 31);  // (32-bit byte offsets into the partial sums: CohBuf)
 }
 
-size_t nhwc_bnhead_extra_bytes(const Plan& pl) {
-    const NhwcGeom g = nhwc_fused_geom(pl);
-    // part | kshift (conv), kshift (identity), gate / cX, c0 | e0, e1 (x 2 with a BatchNorm2d on the skip path) | barrier block
-    return align256((size_t)g.S * kBnFwd * g.P * 4) + align256(4 * g.P * 4) + align256(4 * (size_t)pl.pr.C * 4) + kBarBlock + 256;
-}
-
 namespace {
 NhwcBnArgs make_bn_args(const Plan& pl, const NhwcGeom& ng, int relu, const cnsn_bn_tail_t& bn, const cnsn_bn_tail_t* bn2, float* bn_stats,
-                        void* workspace) {
-    const cnsn_problem_t& p = pl.pr;
+                        const BnHeadWs& w) {
     NhwcBnArgs a{};
     a.f = make_args(pl, ng, relu, kBnGc);
-    a.bn = BnHeadDev{bn.weight, bn.bias, bn.running_mean, bn.running_var, (long long*)bn.num_batches_tracked, bn.eps, bn.momentum};
-    if (bn2)
-        a.bn2 = BnHeadDev{bn2->weight, bn2->bias, bn2->running_mean, bn2->running_var, (long long*)bn2->num_batches_tracked, bn2->eps,
-                          bn2->momentum};
-    const double R = (double)p.N * (double)ng.M;
-    a.inv_r = 1.0 / R;
-    a.unbias_r = R > 1.0 ? R / (R - 1.0) : 1.0;
+    a.bn = bn_head_dev(bn);
+    if (bn2) a.bn2 = bn_head_dev(*bn2);
+    set_bn_count(a, (double)ng.N * (double)ng.M);
     a.bn_stats = bn_stats;
-    a.f.part = (float*)workspace;
-    float* side = (float*)((char*)workspace + align256((size_t)ng.S * kBnFwd * pl.P * 4));
-    a.f.kshift = side;
-    a.kshift_b = side + pl.P;
-    a.f.gout = side + 2 * pl.P;   // forward without `saved`
-    a.f.coefb = side + 2 * pl.P;  // backward: cX, c0
-    a.chan = (float*)((char*)side + align256(4 * pl.P * 4));
+    a.f.part = w.part;
+    a.f.kshift = w.side;
+    a.kshift_b = w.side + pl.P;
+    a.f.gout = w.side + 2 * pl.P;   // forward without `saved`
+    a.f.coefb = w.side + 2 * pl.P;  // backward: cX, c0
+    a.chan = w.chan;
     return a;
 }
-void* bn_bar_block(const Plan& pl, const NhwcBnArgs& a) { return (char*)a.chan + align256(4 * (size_t)pl.pr.C * 4); }
 }  // namespace
+
+size_t nhwc_bnhead_extra_bytes(const Plan& pl) { return bnhead_layout(nhwc_fused_geom(pl), nullptr).bytes; }
 
 int nhwc_bnhead_forward(Plan& pl, int relu, const cnsn_bn_tail_t& bn, const cnsn_bn_tail_t* bn2, const void* conv_out, const void* identity,
                         GateDev gg, void* y, float* saved, float* bn_stats, void* workspace, size_t workspace_bytes, hipStream_t stream) {
-    const cnsn_problem_t& p = pl.pr;
     if (!nhwc_bnhead_ok(pl) || !bn.training || (bn2 && !bn2->training)) return CNSN_E_UNSUPPORTED;
-    if (workspace_bytes < nhwc_bnhead_extra_bytes(pl)) return CNSN_E_WORKSPACE;
     const NhwcGeom ng = nhwc_fused_geom(pl);
-    NhwcBnArgs a = make_bn_args(pl, ng, relu, bn, bn2, bn_stats, workspace);
+    const BnHeadWs w = bnhead_layout(ng, workspace);
+    if (workspace_bytes < w.bytes) return CNSN_E_WORKSPACE;
+    NhwcBnArgs a = make_bn_args(pl, ng, relu, bn, bn2, bn_stats, w);
     a.f.slim = saved;
     if (saved) a.f.gout = saved + (size_t)SL_G * pl.P;
-    a.f.keep = (size_t)2 * pl.P * ng.M * elem_bytes(p.dtype) <= ((size_t)320 << 20) ? 1 : 0;
+    a.f.keep = keep_first_read(2, tensor_bytes(pl));
     int status = CNSN_E_UNSUPPORTED;
-    dispatch_t(p.dtype, [&](auto tt, auto vt) {
+    dispatch_t(pl.pr.dtype, [&](auto tt, auto vt) {
         using T = typename decltype(tt)::type;
         constexpr int VEC = decltype(vt)::value;
         const size_t lds = (size_t)3 * ng.rows * ng.tcb * VEC * 4;
         auto go = [&](auto kern) {
-            status = launch_fused(pl, kern, lds, a, a.f, bn_bar_block(pl, a), stream, (const T*)conv_out, (const T*)identity, (T*)y, gg);
+            status = launch_fused(pl, kern, lds, a, a.f, w.bar, stream, (const T*)conv_out, (const T*)identity, (T*)y, gg);
         };
         if (bn2)
             a.f.keep ? go(nhwc_bnhead_fwd_kernel<T, VEC, true, true>) : go(nhwc_bnhead_fwd_kernel<T, VEC, false, true>);
@@ -234,25 +219,25 @@ int nhwc_bnhead_backward(Plan& pl, int relu, const cnsn_bn_tail_t& bn, const cns
                          const void* identity, GateDev gg, const float* saved, const float* bn_stats, void* d_conv, void* d_identity,
                          GateGradDev dg, float* dbn_w, float* dbn_b, float* dbn2_w, float* dbn2_b, void* workspace,
                          size_t workspace_bytes, hipStream_t stream) {
-    const cnsn_problem_t& p = pl.pr;
     if (!nhwc_bnhead_ok(pl, false) || !bn.training || (bn2 && !bn2->training)) return CNSN_E_UNSUPPORTED;
     if (!saved || !bn_stats || !d_conv || !d_identity || !dbn_w || !dbn_b || (bn2 && (!dbn2_w || !dbn2_b))) return CNSN_E_NULL;
-    if (workspace_bytes < nhwc_bnhead_extra_bytes(pl)) return CNSN_E_WORKSPACE;
     const NhwcGeom ng = nhwc_fused_geom(pl);
-    NhwcBnArgs a = make_bn_args(pl, ng, relu, bn, bn2, const_cast<float*>(bn_stats), workspace);
+    const BnHeadWs w = bnhead_layout(ng, workspace);
+    if (workspace_bytes < w.bytes) return CNSN_E_WORKSPACE;
+    NhwcBnArgs a = make_bn_args(pl, ng, relu, bn, bn2, const_cast<float*>(bn_stats), w);
     a.f.slim = const_cast<float*>(saved);
     a.dbn_w = dbn_w;
     a.dbn_b = dbn_b;
     a.dbn2_w = dbn2_w;
     a.dbn2_b = dbn2_b;
-    a.f.keep = (size_t)3 * pl.P * ng.M * elem_bytes(p.dtype) <= ((size_t)320 << 20) ? 1 : 0;
+    a.f.keep = keep_first_read(3, tensor_bytes(pl));
     int status = CNSN_E_UNSUPPORTED;
-    dispatch_t(p.dtype, [&](auto tt, auto vt) {
+    dispatch_t(pl.pr.dtype, [&](auto tt, auto vt) {
         using T = typename decltype(tt)::type;
         constexpr int VEC = decltype(vt)::value;
         const size_t lds = (size_t)3 * ng.rows * ng.tcb * VEC * 4;
         auto go = [&](auto kern) {
-            status = launch_fused(pl, kern, lds, a, a.f, bn_bar_block(pl, a), stream, (const T*)gy, (const T*)conv_out, (const T*)identity,
+            status = launch_fused(pl, kern, lds, a, a.f, w.bar, stream, (const T*)gy, (const T*)conv_out, (const T*)identity,
                                   (T*)d_conv, (T*)d_identity, gg, dg);
         };
         if (bn2)

@@ -16,11 +16,10 @@ bool has_bn(const cnsn_ibn_t& d) { return d.half < d.C; }
 // the descriptor's shape checks, then the problem the single-launch machinery plans with (SelfNorm's fields unused but for the
 // layout and the context)
 int ibn_parse(const cnsn_ibn_t* d, Plan& pl) {
-    if (!d) return CNSN_E_NULL;
-    if (d->struct_bytes != (int32_t)sizeof(cnsn_ibn_t)) return CNSN_E_STRUCT;
-    if (d->dtype != CNSN_F32 && d->dtype != CNSN_BF16 && d->dtype != CNSN_F16) return CNSN_E_DTYPE;
-    if (d->N <= 0 || d->C <= 0 || d->H <= 0 || d->W <= 0 || d->half < 0 || d->half > d->C) return CNSN_E_SHAPE;
-    if (has_bn(*d) && d->bn.struct_bytes != (int32_t)sizeof(cnsn_bn_tail_t)) return CNSN_E_STRUCT;
+    const int st = parse_desc_head(d);
+    if (st) return st;
+    if (d->half < 0 || d->half > d->C) return CNSN_E_SHAPE;
+    if (has_bn(*d) && parse_bn_tail(d->bn)) return CNSN_E_STRUCT;
     cnsn_problem_t p{};
     p.struct_bytes = (int32_t)sizeof(cnsn_problem_t);
     p.dtype = d->dtype;
@@ -47,23 +46,21 @@ bool ibn_ok(const Plan& pl, const cnsn_ibn_t& d, bool check_health) {
     if (d.half <= 0 || d.half % CNSN_NHWC_GC != 0) return false;  // (a phase-B group is all InstanceNorm or all BatchNorm)
     if (p.N < 2 || p.N > kBlock || p.H * p.W < 2) return false;   // (phase B: a thread per instance)
     if (pl.P * IB_ROWS >= ((size_t)1 << 29)) return false;       // (CohBuf: 32-bit byte offsets)
-    if (check_health) {
-        const int mode = fused_mode();
-        if (mode == 0 || !resident_auto_enabled()) return false;  // (resident_auto_enabled: switched on and not degraded)
-        if (mode > 2 && pl.P * (size_t)(p.H * p.W) * elem_bytes(p.dtype) > ((size_t)mode << 20)) return false;
-    }
+    if (check_health && !single_launch_allowed(tensor_bytes(pl))) return false;
     const NhwcGeom g = nhwc_fused_geom(pl);
     if ((long)g.N * g.S * g.ncb < 8) return false;                // (a grid of at least one workgroup per barrier group)
     return (size_t)g.S * 2 * g.P * 4 < ((size_t)1 << 31);
 }
 
 // part [S][2][P] | kshift [P] | coef [3][P] (forward without `saved`) / cX, c0 (backward) | barrier block
-size_t ibn_extra_bytes(const Plan& pl) {
-    const NhwcGeom g = nhwc_fused_geom(pl);
-    return align256((size_t)g.S * 2 * g.P * 4) + align256(g.P * 4) + align256(3 * g.P * 4) + kBarBlock + 256;
+struct IbnWs { float *part, *kshift, *coefb; void* bar; size_t bytes; };
+IbnWs ibn_layout(const NhwcGeom& g, void* workspace) {
+    Carver c(workspace);
+    return {c.take((size_t)g.S * 2 * g.P * 4), c.take(g.P * 4), c.take(3 * g.P * 4), c.take<void>(kBarBlock), c.bytes()};
 }
+size_t ibn_extra_bytes(const Plan& pl) { return ibn_layout(nhwc_fused_geom(pl), nullptr).bytes; }
 
-NhwcIbnArgs make_ibn_args(const Plan& pl, const NhwcGeom& ng, const cnsn_ibn_t& d, int gc, void* workspace) {
+NhwcIbnArgs make_ibn_args(const Plan& pl, const NhwcGeom& ng, const cnsn_ibn_t& d, int gc, const IbnWs& w) {
     NhwcIbnArgs a{};
     a.f = make_args(pl, ng, d.relu ? 1 : 0, gc);
     a.f.training = has_bn(d) && d.bn.training ? 1 : 0;
@@ -71,33 +68,26 @@ NhwcIbnArgs make_ibn_args(const Plan& pl, const NhwcGeom& ng, const cnsn_ibn_t& 
     a.eps_in = d.eps_in;
     a.in_w = d.in_weight;
     a.in_b = d.in_bias;
-    if (has_bn(d))
-        a.bn = BnHeadDev{d.bn.weight, d.bn.bias, d.bn.running_mean, d.bn.running_var, (long long*)d.bn.num_batches_tracked, d.bn.eps,
-                         d.bn.momentum};
-    const double R = (double)ng.N * (double)ng.M;
-    a.inv_r = 1.0 / R;
-    a.unbias_r = R > 1.0 ? R / (R - 1.0) : 1.0;
-    a.f.part = (float*)workspace;
-    a.f.kshift = (float*)((char*)workspace + align256((size_t)ng.S * 2 * pl.P * 4));
-    a.f.coefb = (float*)((char*)a.f.kshift + align256(pl.P * 4));
+    if (has_bn(d)) a.bn = bn_head_dev(d.bn);
+    set_bn_count(a, (double)ng.N * (double)ng.M);
+    a.f.part = w.part;
+    a.f.kshift = w.kshift;
+    a.f.coefb = w.coefb;
     return a;
 }
-void* ibn_bar_block(const Plan& pl, const NhwcIbnArgs& a) { return (char*)a.f.coefb + align256(3 * pl.P * 4); }
-
-bool aligned16(const void* p) { return ((uintptr_t)p & 15u) == 0; }
 
 }  // namespace
 
 int nhwc_ibn_forward(Plan& pl, const cnsn_ibn_t& d, const void* x, const void* addend, void* y, float* saved, void* workspace,
                      hipStream_t stream) {
-    const cnsn_problem_t& p = pl.pr;
     const NhwcGeom ng = nhwc_fused_geom(pl);
-    NhwcIbnArgs a = make_ibn_args(pl, ng, d, CNSN_NHWC_GC, workspace);
+    const IbnWs w = ibn_layout(ng, workspace);
+    NhwcIbnArgs a = make_ibn_args(pl, ng, d, CNSN_NHWC_GC, w);
     a.saved = saved;
     a.coef = saved ? saved : a.f.coefb;
-    a.f.keep = (size_t)(addend ? 2 : 1) * pl.P * ng.M * elem_bytes(p.dtype) <= ((size_t)320 << 20) ? 1 : 0;
+    a.f.keep = keep_first_read(addend ? 2 : 1, tensor_bytes(pl));
     int status = CNSN_E_UNSUPPORTED;
-    dispatch_t(p.dtype, [&](auto tt, auto vt) {
+    dispatch_t(pl.pr.dtype, [&](auto tt, auto vt) {
         using T = typename decltype(tt)::type;
         constexpr int VEC = decltype(vt)::value;
         const size_t lds = (size_t)2 * ng.rows * ng.tcb * VEC * 4;
@@ -105,7 +95,7 @@ int nhwc_ibn_forward(Plan& pl, const cnsn_ibn_t& d, const void* x, const void* a
             constexpr int ADD = decltype(at)::value;
             if constexpr (ADD != ADD_POST) {
                 auto go = [&](auto kern) {
-                    status = launch_fused(pl, kern, lds, a, a.f, ibn_bar_block(pl, a), stream, (const T*)x, (const T*)addend, (T*)y);
+                    status = launch_fused(pl, kern, lds, a, a.f, w.bar, stream, (const T*)x, (const T*)addend, (T*)y);
                 };
                 a.f.keep ? go(nhwc_ibn_fwd_kernel<T, VEC, ADD, true>) : go(nhwc_ibn_fwd_kernel<T, VEC, ADD, false>);
             }
@@ -119,19 +109,19 @@ int nhwc_ibn_forward(Plan& pl, const cnsn_ibn_t& d, const void* x, const void* a
 
 int nhwc_ibn_backward(Plan& pl, const cnsn_ibn_t& d, const void* gy, const void* x, const void* addend, const float* saved, void* dx,
                       float* d_in_w, float* d_in_b, float* d_bn_w, float* d_bn_b, void* workspace, hipStream_t stream) {
-    const cnsn_problem_t& p = pl.pr;
     const NhwcGeom ng = nhwc_fused_geom(pl);
-    NhwcIbnArgs a = make_ibn_args(pl, ng, d, CNSN_NHWC_GC_BWD, workspace);
+    const IbnWs w = ibn_layout(ng, workspace);
+    NhwcIbnArgs a = make_ibn_args(pl, ng, d, CNSN_NHWC_GC_BWD, w);
     a.saved = const_cast<float*>(saved);
     a.d_in_w = d_in_w;
     a.d_in_b = d_in_b;
     a.d_bn_w = d_bn_w;
     a.d_bn_b = d_bn_b;
-    a.f.keep = (size_t)(addend ? 3 : 2) * pl.P * ng.M * elem_bytes(p.dtype) <= ((size_t)320 << 20) ? 1 : 0;
+    a.f.keep = keep_first_read(addend ? 3 : 2, tensor_bytes(pl));
     // launch_fused cannot decline a call ibn_ok(pl, d, false) accepts: the grid is occupancy (>= 1: no scratch, 128 VGPRs) x at
     // least 8 compute units (grid_for keeps 8 whatever the head-room), a multiple of 8 and at most the tiles, which are >= 8 here
     int status = CNSN_E_UNSUPPORTED;
-    dispatch_t(p.dtype, [&](auto tt, auto vt) {
+    dispatch_t(pl.pr.dtype, [&](auto tt, auto vt) {
         using T = typename decltype(tt)::type;
         constexpr int VEC = decltype(vt)::value;
         const size_t lds = (size_t)2 * ng.rows * ng.tcb * VEC * 4;
@@ -139,7 +129,7 @@ int nhwc_ibn_backward(Plan& pl, const cnsn_ibn_t& d, const void* gy, const void*
             constexpr int ADD = decltype(at)::value;
             if constexpr (ADD != ADD_POST) {
                 auto go = [&](auto kern) {
-                    status = launch_fused(pl, kern, lds, a, a.f, ibn_bar_block(pl, a), stream, (const T*)gy, (const T*)x, (const T*)addend,
+                    status = launch_fused(pl, kern, lds, a, a.f, w.bar, stream, (const T*)gy, (const T*)x, (const T*)addend,
                                           (T*)dx);
                 };
                 a.f.keep ? go(nhwc_ibn_bwd_kernel<T, VEC, ADD, true>) : go(nhwc_ibn_bwd_kernel<T, VEC, ADD, false>);

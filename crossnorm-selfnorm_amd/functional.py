@@ -45,7 +45,6 @@ _resident_set = None        # what set_resident() last asked for (None: never ca
 def resident_allowed() -> bool:
     """whether CNSN_STRATEGY_AUTO may currently choose the cluster kernels as far as the SWITCH goes (`set_resident`, else
     CNSN_RESIDENT at load); a degradation after a time-out is separate (`cnsn_resident_degraded`)"""
-    import os
     return _resident_set if _resident_set is not None else os.environ.get("CNSN_RESIDENT", "1") != "0"
 
 
@@ -80,7 +79,6 @@ def _nhwc_call(x: torch.Tensor, cfg, chan_perm) -> bool:
     Everything else is copied to NCHW, like the reference's `.contiguous()` (models/cnsn.py:14).  CNSN_NHWC=0 switches it off."""
     global NHWC
     if NHWC is None:
-        import os
         NHWC = os.environ.get("CNSN_NHWC") != "0"
     if not NHWC or x.dim() != 4 or chan_perm is not None or cfg.content_box is not None or cfg.style_box is not None:
         return False
@@ -133,6 +131,67 @@ def _f32(t: torch.Tensor) -> torch.Tensor:
     return t.detach().to(torch.float32).contiguous()
 
 
+# ---- the skeleton the autograd classes below share
+def _addend_like(x, addend, what, dense, name="addend"):
+    """the second input of a call, checked against the dense `x` and made dense like it"""
+    _require_device(addend, f"{what}({name})")
+    assert addend.shape == x.shape and addend.dtype == x.dtype, f"{name} must match the first input"
+    return dense(addend)
+
+
+def _cl_inputs(x, addend, what):
+    """x and the optional addend of a single launch as dense channels-last tensors"""
+    x = _dense_cl(x)
+    return x, (None if addend is None else _addend_like(x, addend, what, _dense_cl))
+
+
+def _workspace(nbytes: int, dev) -> torch.Tensor:
+    return torch.empty(nbytes // 4 + 4, dtype=torch.float32, device=dev)
+
+
+def _grad_like(gy, x, cl: bool):
+    """the incoming gradient in x's dtype, dense in x's layout"""
+    gy = gy if gy.dtype == x.dtype else gy.to(x.dtype)
+    return _dense_cl(gy) if cl else _dense(gy)
+
+
+def _cast_grads(tensors, dtypes):
+    """float32 parameter gradients in the parameters' dtypes (None where there is no parameter)"""
+    return [None if d is None else (t if t.dtype == d else t.to(d)) for t, d in zip(tensors, dtypes)]
+
+
+def _gate_grad_views(c: int, dev, extra: int = 0):
+    """one allocation for a gate's gradients — d_fc_weight (C,1,2), d_bn_weight (C), d_bn_bias (C) — and `extra` more rows of C
+    floats behind them: (the views, the cnsn_gate_grad_t that points at the first three)"""
+    flat = torch.empty((4 + extra) * c, dtype=torch.float32, device=dev)
+    rows = [flat[:2 * c].view(c, 1, 2), *flat[2 * c:].view(2 + extra, c).unbind(0)]
+    return rows, _ffi.GateGrad(_ptr(rows[0]), _ptr(rows[1]), _ptr(rows[2]))
+
+
+def _plan_cache() -> dict:
+    """remembered planning answers, emptied when a knob moves (_ffi.forget_plans)"""
+    cache = {}
+    _ffi._plan_caches.append(cache)
+    return cache
+
+
+def _remembered(cache: dict, key, ask) -> bool:
+    hit = cache.get(key)
+    if hit is None:
+        hit = cache[key] = bool(ask())
+    return hit
+
+
+def _single_launch_tensor(x, poll: bool = True) -> bool:
+    """what every single-launch plan asks first: a HIP tensor, 4-D, a supported dtype, strictly channels-last, and no persistent
+    launch that gave up without anybody re-arming since (`poll`)"""
+    if not x.is_cuda or x.dim() != 4 or x.dtype not in _DTYPES:
+        return False
+    if not x.is_contiguous(memory_format=torch.channels_last) or x.is_contiguous():
+        return False
+    return not (poll and _ffi.lib().cnsn_resident_degraded())
+
+
 # The module-level caches below are shared by every thread that calls into the library — torch.nn.DataParallel, the
 # reference's own multi-GPU mode (cifar.py:395, imagenet.py:533), runs one Python thread per replica.  Dictionary reads
 # and writes are atomic under the GIL; the read-modify-write sequences (growing the exchange context, taking a slot of
@@ -140,8 +199,7 @@ def _f32(t: torch.Tensor) -> torch.Tensor:
 _lock = threading.RLock()
 
 # sizes of the caller-owned side buffers per problem signature (two ctypes calls saved per launch)
-_size_cache = {}
-_ffi._plan_caches.append(_size_cache)
+_size_cache = _plan_cache()
 
 
 def _sizes(prob):
@@ -189,6 +247,16 @@ def _grow_context(need, dev):
             _retired_contexts.append(have)
         _contexts[dev.index] = have = buf
     return have
+
+
+def _nhwc_context(x):
+    """(pointer, bytes) of the persistent context for a single launch on the channels-last `x` — the IBN and BatchNorm2d + ReLU
+    descriptors carry no problem of their own, so the buffer is sized as for SelfNorm on the same tensor; (None, 0) while the
+    stream is being captured"""
+    prob = _problem(x, FusedConfig(sn_active=True))
+    prob.layout = _ffi.LAYOUT_NHWC
+    _context(prob, x.device)
+    return prob.context, prob.context_bytes
 
 
 class _PinnedRing:
@@ -291,12 +359,10 @@ def which_path(x: torch.Tensor, cfg: FusedConfig, backward: bool = False, chan_p
     return _ffi.PATHS[st]
 
 
-_perm_inline_cache = {}
-_ffi._plan_caches.append(_perm_inline_cache)
+_perm_inline_cache = _plan_cache()
 # A/B switch (profiles/r04_launches_per_step.md): CNSN_LEGACY_LAUNCHES=1 restores the two small launches in front of the op —
 # `num_batches_tracked.add_(1)` as a torch launch and the permutation as a host-to-device copy
-import os as _os  # noqa: E402
-LEGACY_LAUNCHES = _os.environ.get("CNSN_LEGACY_LAUNCHES") == "1"
+LEGACY_LAUNCHES = os.environ.get("CNSN_LEGACY_LAUNCHES") == "1"
 
 
 def perm_inline_ok(x: torch.Tensor, cfg: FusedConfig, perm, chan_perm) -> bool:
@@ -308,11 +374,8 @@ def perm_inline_ok(x: torch.Tensor, cfg: FusedConfig, perm, chan_perm) -> bool:
         return False
     key = (tuple(x.shape), x.dtype, x.device.index, cfg.sn_active, cfg.sn_two, cfg.sn_training, cfg.content_box is not None,
            cfg.style_box is not None, cfg.add_mode, cfg.relu, _strategy)
-    hit = _perm_inline_cache.get(key)
-    if hit is None:
-        hit = which_path(x, cfg, False) == "resident" and which_path(x, cfg, True) == "resident"
-        _perm_inline_cache[key] = hit
-    return hit
+    return _remembered(_perm_inline_cache, key,
+                       lambda: which_path(x, cfg, False) == "resident" and which_path(x, cfg, True) == "resident")
 
 
 def sn_cluster(x: torch.Tensor, cfg: FusedConfig, backward: bool = False) -> bool:
@@ -343,27 +406,52 @@ def _problem(x: torch.Tensor, cfg: FusedConfig) -> _ffi.Problem:
     return p
 
 
-class _GateBuffers:
+class _RunningBuffers:
+    """a BatchNorm's running statistics and counter as the kernels take them.  `direct`: the buffers themselves (contiguous
+    float32), else float32 copies that `write_back` copies into the module's after a training-mode launch.  `nbt`: the counter
+    for the kernel to add 1 to — a counter it cannot reach (not ONE int64 on the device) is counted here, as
+    nn.BatchNorm2d.forward does, and only in training mode; eval mode moves no counter and writes nothing back."""
+
+    def _take_running(self, rm, rv, nbt, training=True):
+        self.src_rm, self.src_rv, self.training = rm, rv, bool(training)
+        self.direct = rm.dtype == torch.float32 and rm.is_contiguous() and rv.dtype == torch.float32 and rv.is_contiguous()
+        self.rm = rm.detach() if self.direct else _f32(rm)
+        self.rv = rv.detach() if self.direct else _f32(rv)
+        if nbt is not None and not (training and nbt.dtype == torch.int64 and nbt.is_cuda and nbt.numel() == 1):
+            if training:
+                nbt.add_(1)
+            nbt = None
+        self.nbt = nbt
+
+    def write_back(self):
+        if self.training and not self.direct:
+            self.src_rm.copy_(self.rm)
+            self.src_rv.copy_(self.rv)
+
+
+class _GateBuffers(_RunningBuffers):
     """float32 contiguous views/copies of a gate's tensors + the cnsn_gate_t that points at them."""
 
     def __init__(self, w, gamma, beta, rm, rv, nbt=None):
-        self.src_rm, self.src_rv = rm, rv
         self.w, self.gamma, self.beta = _f32(w), _f32(gamma), _f32(beta)
-        direct = rm.dtype == torch.float32 and rm.is_contiguous() and rv.dtype == torch.float32 \
-            and rv.is_contiguous()
-        self.rm = rm.detach() if direct else _f32(rm)
-        self.rv = rv.detach() if direct else _f32(rv)
-        self.direct = direct
-        if nbt is not None and not (nbt.dtype == torch.int64 and nbt.is_cuda and nbt.numel() == 1):
-            nbt.add_(1)          # (a counter the kernel cannot reach: counted here, as nn.BatchNorm1d.forward does)
-            nbt = None
-        self.nbt = nbt
-        self.c = _ffi.Gate(_ptr(self.w), _ptr(self.gamma), _ptr(self.beta), _ptr(self.rm), _ptr(self.rv), _ptr(nbt))
+        self._take_running(rm, rv, nbt)
+        self.c = _ffi.Gate(_ptr(self.w), _ptr(self.gamma), _ptr(self.beta), _ptr(self.rm), _ptr(self.rv), _ptr(self.nbt))
 
-    def write_back(self):
-        if not self.direct:  # running buffers kept in another dtype: copy the update back
-            self.src_rm.copy_(self.rm)
-            self.src_rv.copy_(self.rv)
+
+class _Bn2dBuffers(_RunningBuffers):
+    """float32 contiguous views / copies of an nn.BatchNorm2d's tensors + the cnsn_bn_tail_t that points at them: the one place a
+    BatchNorm2d module is marshalled for the library"""
+
+    def __init__(self, w, b, rm, rv, eps, momentum, nbt, training=True):
+        self.w, self.b = _f32(w), _f32(b)
+        self.eps, self.momentum = float(eps), float(momentum)
+        self._take_running(rm, rv, nbt, training)
+        self.c = self.struct(self.nbt)
+
+    def struct(self, nbt=None):
+        """(without the counter: what a backward passes)"""
+        return _ffi.BnTail(C.sizeof(_ffi.BnTail), int(self.training), self.eps, self.momentum, self.w.data_ptr(), self.b.data_ptr(),
+                           self.rm.data_ptr(), self.rv.data_ptr(), _ptr(nbt))
 
 
 class FusedCNSN(torch.autograd.Function):
@@ -384,12 +472,7 @@ class FusedCNSN(torch.autograd.Function):
         _ffi.check_resident_health("cnsn_forward")
         nhwc = _nhwc_call(x, cfg, chan_perm if cfg.cn_active else None)
         x = x if nhwc else _dense(x)                               # reference cnsn.py:14 (a channels-last call is computed where it lies)
-        if cfg.add_mode != "none":
-            _require_device(addend, "cnsn_forward(addend)")
-            assert addend.shape == x.shape and addend.dtype == x.dtype, "addend must match x"
-            addend = _dense_cl(addend) if nhwc else _dense(addend)
-        else:
-            addend = None
+        addend = _addend_like(x, addend, "cnsn_forward", _dense_cl if nhwc else _dense) if cfg.add_mode != "none" else None
         prob = _problem(x, cfg)
         prob.layout = _ffi.LAYOUT_NHWC if nhwc else _ffi.LAYOUT_NCHW
         dev = x.device
@@ -412,7 +495,7 @@ class FusedCNSN(torch.autograd.Function):
         need_bwd = any(ctx.needs_input_grad)
         saved_floats, ws_bytes = _sizes(prob)[:2]
         saved = torch.empty(saved_floats, dtype=torch.float32, device=dev) if need_bwd else None
-        ws = torch.empty(ws_bytes // 4 + 4, dtype=torch.float32, device=dev)
+        ws = _workspace(ws_bytes, dev)
         epi = _epilogue(cfg, addend) if cfg.has_epilogue else None
         # A PRE add in front of a channels-last call (two tensor passes each way): the forward KEEPS X = x + addend and the
         # backward reads that one tensor instead of two, twice (cnsn_epilogue_t.sum_out).  X is what the reference's in-place
@@ -462,29 +545,20 @@ class FusedCNSN(torch.autograd.Function):
         x, saved, perm, chan_perm, addend = ctx.saved_tensors
         cfg, prob = ctx.cfg, ctx.prob
         gate_g, gate_f = ctx.gates
-        if gy.dtype != x.dtype:
-            gy = gy.to(x.dtype)
-        gy = _dense_cl(gy) if prob.layout == _ffi.LAYOUT_NHWC else _dense(gy)
+        gy = _grad_like(gy, x, prob.layout == _ffi.LAYOUT_NHWC)
         dev = x.device
         dx = _out_like(x)
         ws_bytes = _sizes(prob)[1]
         _context(prob, dev)     # (the buffer may have grown since the forward; None under graph capture)
         if torch.cuda.is_current_stream_capturing():
             prob.context, prob.context_bytes = None, 0
-        ws = torch.empty(ws_bytes // 4 + 4, dtype=torch.float32, device=dev)
-        Cn = x.shape[1]
-
-        def grads():  # one allocation, three views: d_fc_weight (C,1,2), d_bn_weight (C), d_bn_bias (C)
-            flat = torch.empty(4 * Cn, dtype=torch.float32, device=dev)
-            dw, dgam, dbet = flat[:2 * Cn].view(Cn, 1, 2), flat[2 * Cn:3 * Cn], flat[3 * Cn:]
-            return (dw, dgam, dbet), _ffi.GateGrad(_ptr(dw), _ptr(dgam), _ptr(dbet))
-
+        ws = _workspace(ws_bytes, dev)
         gg = gf = None
         gg_c = gf_c = None
         if cfg.sn_active:
-            gg, gg_c = grads()
+            gg, gg_c = _gate_grad_views(x.shape[1], dev)
             if cfg.sn_two:
-                gf, gf_c = grads()
+                gf, gf_c = _gate_grad_views(x.shape[1], dev)
         epi = _epilogue(cfg, addend) if cfg.has_epilogue else None
         d_add = None
         if cfg.add_mode == "post":      # gradient of a POST addend: grad_y behind the ReLU mask
@@ -508,9 +582,8 @@ class FusedCNSN(torch.autograd.Function):
         if cfg.add_mode == "pre" or ctx.kept_sum:       # d(x + addend) reaches both terms unchanged
             d_add = dx
         pd = ctx.param_dtypes
-        out_g = [None] * 3 if gg is None else [t if t.dtype == pd[i] else t.to(pd[i]) for i, t in enumerate(gg)]
-        out_f = [None] * 3 if gf is None else [t if t.dtype == pd[3 + i] else t.to(pd[3 + i])
-                                               for i, t in enumerate(gf)]
+        out_g = [None] * 3 if gg is None else _cast_grads(gg, pd[:3])
+        out_f = [None] * 3 if gf is None else _cast_grads(gf, pd[3:])
         #      x   cfg  perm  chan  g_w..g_beta   g_rm g_rv   f_w..f_beta  f_rm f_rv  addend  g_nbt f_nbt
         return (dx, None, None, None, *out_g, None, None, *out_f, None, None, d_add, None, None)
 
@@ -539,49 +612,30 @@ class FusedCNSNTail(torch.autograd.Function):
             lib = _ffi.lib()
             _ffi.check_resident_health("cnsn_forward_bnrelu")
             x = _dense(x)
-            if cfg.add_mode != "none":
-                _require_device(addend, "cnsn_forward_bnrelu(addend)")
-                assert addend.shape == x.shape and addend.dtype == x.dtype, "addend must match x"
-                addend = _dense(addend)
-            else:
-                addend = None
+            addend = _addend_like(x, addend, "cnsn_forward_bnrelu", _dense) if cfg.add_mode != "none" else None
             prob = _problem(x, cfg)
             dev = x.device
             gate = _GateBuffers(g_w, g_gamma, g_beta, g_rm, g_rv, g_nbt if cfg.sn_training else None)
-            bw, bb = _f32(bn_w), _f32(bn_b)
-            if bn_nbt is not None and not (bn_training and bn_nbt.dtype == torch.int64 and bn_nbt.is_cuda):
-                if bn_training:
-                    bn_nbt.add_(1)
-                bn_nbt = None
-            direct = (bn_rm.dtype == torch.float32 and bn_rm.is_contiguous() and bn_rv.dtype == torch.float32
-                      and bn_rv.is_contiguous())
-            rm = bn_rm.detach() if direct else _f32(bn_rm)
-            rv = bn_rv.detach() if direct else _f32(bn_rv)
-            tail = _ffi.BnTail(C.sizeof(_ffi.BnTail), int(bn_training), float(bn_eps), float(bn_momentum), bw.data_ptr(),
-                               bb.data_ptr(), rm.data_ptr(), rv.data_ptr(), _ptr(bn_nbt))
+            bn = _Bn2dBuffers(bn_w, bn_b, bn_rm, bn_rv, bn_eps, bn_momentum, bn_nbt, bn_training)
             y = _out_like(x) if want_y else None
             z = _out_like(x)
             need_bwd = any(ctx.needs_input_grad)
             saved_floats, ws_bytes = _sizes(prob)[:2]
             saved = torch.empty(saved_floats, dtype=torch.float32, device=dev) if need_bwd else None
             stats = torch.empty(2 * x.shape[1], dtype=torch.float32, device=dev)
-            ws = torch.empty(ws_bytes // 4, dtype=torch.float32, device=dev)
+            ws = _workspace(ws_bytes, dev)
             epi = _epilogue(cfg, addend) if cfg.has_epilogue else None
-            st = lib.cnsn_forward_bnrelu(C.byref(prob), C.byref(epi) if epi else None, C.byref(tail), _ptr(x),
+            st = lib.cnsn_forward_bnrelu(C.byref(prob), C.byref(epi) if epi else None, C.byref(bn.c), _ptr(x),
                                          C.byref(gate.c), _ptr(y), _ptr(z), _ptr(saved), _ptr(stats), _ptr(ws), ws_bytes,
                                          _stream(x))
             _ffi.check(st, "cnsn_forward_bnrelu")
             if cfg.sn_training:
                 gate.write_back()
-            if bn_training and not direct:
-                bn_rm.copy_(rm)
-                bn_rv.copy_(rv)
+            bn.write_back()
             ctx.set_materialize_grads(False)    # an unused y hands None to the backward, not a tensor of zeros
             if need_bwd:
-                ctx.cfg, ctx.prob, ctx.gate, ctx.want_y = cfg, prob, gate, want_y
-                ctx.tail_cfg = (bool(bn_training), float(bn_eps), float(bn_momentum))
+                ctx.cfg, ctx.prob, ctx.gate, ctx.bn, ctx.want_y = cfg, prob, gate, bn, want_y
                 ctx.param_dtypes = (g_w.dtype, g_gamma.dtype, g_beta.dtype, bn_w.dtype, bn_b.dtype)
-                ctx.bn_buffers = (bw, bb, rm, rv)
                 ctx.save_for_backward(x, saved, addend, stats)
             return (y, z) if want_y else z
 
@@ -593,30 +647,21 @@ class FusedCNSNTail(torch.autograd.Function):
             lib = _ffi.lib()
             cfg, prob, gate = ctx.cfg, ctx.prob, ctx.gate
             dev = x.device
-            if gz is None:
-                gz = torch.zeros_like(x)
-            gz = _dense(gz.to(x.dtype))
+            gz = _grad_like(gz if gz is not None else torch.zeros_like(x), x, False)
             if gy is not None:
-                gy = _dense(gy.to(x.dtype))
-            bw, bb, rm, rv = ctx.bn_buffers
-            tr, eps, mom = ctx.tail_cfg
-            tail = _ffi.BnTail(C.sizeof(_ffi.BnTail), int(tr), eps, mom, bw.data_ptr(), bb.data_ptr(), rm.data_ptr(),
-                               rv.data_ptr(), None)
-            Cn = x.shape[1]
+                gy = _grad_like(gy, x, False)
+            tail = ctx.bn.struct()
             dx = _out_like(x)
-            flat = torch.empty(6 * Cn, dtype=torch.float32, device=dev)
-            dw, dgam, dbet = flat[:2 * Cn].view(Cn, 1, 2), flat[2 * Cn:3 * Cn], flat[3 * Cn:4 * Cn]
-            dbw, dbb = flat[4 * Cn:5 * Cn], flat[5 * Cn:]
-            gg = _ffi.GateGrad(_ptr(dw), _ptr(dgam), _ptr(dbet))
+            grads, gg = _gate_grad_views(x.shape[1], dev, 2)
+            dbw, dbb = grads[3:]
             ws_bytes = _sizes(prob)[1]
-            ws = torch.empty(ws_bytes // 4, dtype=torch.float32, device=dev)
+            ws = _workspace(ws_bytes, dev)
             epi = _epilogue(cfg, addend) if cfg.has_epilogue else None
             st = lib.cnsn_backward_bnrelu(C.byref(prob), C.byref(epi) if epi else None, C.byref(tail), _ptr(gy), _ptr(gz),
                                           _ptr(x), C.byref(gate.c), _ptr(saved), _ptr(stats), _ptr(dx), C.byref(gg),
                                           _ptr(dbw), _ptr(dbb), _ptr(ws), ws_bytes, _stream(x))
             _ffi.check(st, "cnsn_backward_bnrelu")
-            pd = ctx.param_dtypes
-            outs = [t if t.dtype == pd[i] else t.to(pd[i]) for i, t in enumerate((dw, dgam, dbet, dbw, dbb))]
+            outs = _cast_grads(grads, ctx.param_dtypes)
             d_add = dx if cfg.add_mode == "pre" else None
             #       x   cfg   addend want_y  g_w      g_gamma  g_beta  g_rm  g_rv  bn_w     bn_b    bn_rm bn_rv  tr   eps  mom  nbt nbt
             return (dx, None, d_add, None, outs[0], outs[1], outs[2], None, None, outs[3], outs[4], None, None, None, None, None,
@@ -627,8 +672,7 @@ class FusedCNSNTail(torch.autograd.Function):
 # the block's last BatchNorm2d in front of the op: y = act(SelfNorm(BatchNorm2d(conv_out) + identity))
 # (cnsn_forward_bn_block / cnsn_backward_bn_block, csrc/cnsn_nhwc_bnhead_kernels.h)
 # ------------------------------------------------------------------------------------------------
-_bn_block_plan_cache = {}
-_ffi._plan_caches.append(_bn_block_plan_cache)
+_bn_block_plan_cache = _plan_cache()
 # CNSN_BN_BLOCK=0: never fold the block's last BatchNorm2d into the op's launch (A/B knob)
 _BN_BLOCK = os.environ.get("CNSN_BN_BLOCK", "1") != "0"
 
@@ -637,46 +681,14 @@ def bn_block_plan(x: torch.Tensor, cfg: FusedConfig) -> bool:
     """True when ONE launch per direction evaluates `act(CNSN(BatchNorm2d(conv_out) + identity))` for this tensor / configuration
     (cnsn_bn_block_plan: channels-last, SelfNorm alone with one gate in training mode, N <= 256, no stream capture) —
     remembered per (shape, dtype, configuration, strategy)."""
-    if not _BN_BLOCK or not x.is_cuda or x.dim() != 4 or x.dtype not in _DTYPES or cfg.cn_active or not cfg.sn_training:
+    if not _BN_BLOCK or cfg.cn_active or not cfg.sn_training or not _single_launch_tensor(x):   # (degraded: the un-fused sequence)
         return False
-    if not x.is_contiguous(memory_format=torch.channels_last) or x.is_contiguous():
-        return False
-    if _ffi.lib().cnsn_resident_degraded():      # (a persistent launch gave up and nobody re-armed since: the un-fused sequence)
-        return False
-    key = (tuple(x.shape), x.dtype, x.device.index, cfg.relu, cfg.sn_two, _strategy)
-    hit = _bn_block_plan_cache.get(key)
-    if hit is None:
+
+    def ask():
         prob = _problem(x, cfg)
         prob.layout = _ffi.LAYOUT_NHWC
-        epi = _epilogue(cfg, None)
-        hit = _ffi.lib().cnsn_bn_block_plan(C.byref(prob), C.byref(epi)) == 1
-        _bn_block_plan_cache[key] = hit
-    return hit
-
-
-class _Bn2dBuffers:
-    """float32 contiguous views / copies of an nn.BatchNorm2d's tensors + the cnsn_bn_tail_t that points at them (training mode)"""
-
-    def __init__(self, w, b, rm, rv, eps, momentum, nbt):
-        self.src_rm, self.src_rv = rm, rv
-        self.w, self.b = _f32(w), _f32(b)
-        if nbt is not None and not (nbt.dtype == torch.int64 and nbt.is_cuda and nbt.numel() == 1):
-            nbt.add_(1)          # (a counter the kernel cannot reach: counted here, as nn.BatchNorm2d.forward does)
-            nbt = None
-        self.direct = rm.dtype == torch.float32 and rm.is_contiguous() and rv.dtype == torch.float32 and rv.is_contiguous()
-        self.rm = rm.detach() if self.direct else _f32(rm)
-        self.rv = rv.detach() if self.direct else _f32(rv)
-        self.eps, self.momentum = float(eps), float(momentum)
-        self.c = self.struct(nbt)
-
-    def struct(self, nbt=None):
-        return _ffi.BnTail(C.sizeof(_ffi.BnTail), 1, self.eps, self.momentum, self.w.data_ptr(), self.b.data_ptr(), self.rm.data_ptr(),
-                           self.rv.data_ptr(), _ptr(nbt))
-
-    def write_back(self):
-        if not self.direct:
-            self.src_rm.copy_(self.rm)
-            self.src_rv.copy_(self.rv)
+        return _ffi.lib().cnsn_bn_block_plan(C.byref(prob), C.byref(_epilogue(cfg, None))) == 1
+    return _remembered(_bn_block_plan_cache, (tuple(x.shape), x.dtype, x.device.index, cfg.relu, cfg.sn_two, _strategy), ask)
 
 
 class FusedBnBlock(torch.autograd.Function):
@@ -694,9 +706,7 @@ class FusedBnBlock(torch.autograd.Function):
             lib = _ffi.lib()
             _ffi.check_resident_health("cnsn_forward_bn_block")
             x = _dense_cl(conv_out)
-            _require_device(identity, "cnsn_forward_bn_block(identity)")
-            assert identity.shape == x.shape and identity.dtype == x.dtype, "identity must match conv_out"
-            idt = _dense_cl(identity)
+            idt = _addend_like(x, identity, "cnsn_forward_bn_block", _dense_cl, "identity")
             prob = _problem(x, cfg)
             prob.layout = _ffi.LAYOUT_NHWC
             dev = x.device
@@ -709,7 +719,7 @@ class FusedBnBlock(torch.autograd.Function):
             saved_floats, ws_bytes = _sizes(prob)[:2]
             saved = torch.empty(saved_floats, dtype=torch.float32, device=dev) if need_bwd else None
             stats = torch.empty((8 if skip else 4) * x.shape[1], dtype=torch.float32, device=dev)
-            ws = torch.empty(ws_bytes // 4 + 4, dtype=torch.float32, device=dev)
+            ws = _workspace(ws_bytes, dev)
             epi = _epilogue(cfg, idt)
             st = lib.cnsn_forward_bn_block(C.byref(prob), C.byref(epi), C.byref(head.c), C.byref(skip.c) if skip else None, _ptr(x),
                                            C.byref(gate.c), _ptr(y), _ptr(saved), _ptr(stats), _ptr(ws), ws_bytes, _stream(x))
@@ -732,45 +742,39 @@ class FusedBnBlock(torch.autograd.Function):
             lib = _ffi.lib()
             cfg, prob, gate, head, skip = ctx.cfg, ctx.prob, ctx.gate, ctx.head, ctx.skip
             dev = x.device
-            gy = _dense_cl(gy if gy.dtype == x.dtype else gy.to(x.dtype))
+            gy = _grad_like(gy, x, True)
             hs = head.struct()
             ss = skip.struct() if skip else None
-            Cn = x.shape[1]
             d_conv, d_idt = _out_like(x), _out_like(x)
-            flat = torch.empty(8 * Cn, dtype=torch.float32, device=dev)
-            dw, dgam, dbet = flat[:2 * Cn].view(Cn, 1, 2), flat[2 * Cn:3 * Cn], flat[3 * Cn:4 * Cn]
-            dbw, dbb, d2w, d2b = flat[4 * Cn:5 * Cn], flat[5 * Cn:6 * Cn], flat[6 * Cn:7 * Cn], flat[7 * Cn:]
-            gg = _ffi.GateGrad(_ptr(dw), _ptr(dgam), _ptr(dbet))
+            grads, gg = _gate_grad_views(x.shape[1], dev, 4)
+            dbw, dbb, d2w, d2b = grads[3:]
             ws_bytes = _sizes(prob)[1]
             _context(prob, dev)
             if torch.cuda.is_current_stream_capturing():
                 prob.context, prob.context_bytes = None, 0
-            ws = torch.empty(ws_bytes // 4 + 4, dtype=torch.float32, device=dev)
+            ws = _workspace(ws_bytes, dev)
             epi = _epilogue(cfg, idt)
             st = lib.cnsn_backward_bn_block(C.byref(prob), C.byref(epi), C.byref(hs), C.byref(ss) if ss else None, _ptr(gy), _ptr(x),
                                             C.byref(gate.c), _ptr(saved), _ptr(stats), _ptr(d_conv), _ptr(d_idt), C.byref(gg),
                                             _ptr(dbw), _ptr(dbb), _ptr(d2w) if skip else None, _ptr(d2b) if skip else None, _ptr(ws),
                                             ws_bytes, _stream(x))
             _ffi.check(st, "cnsn_backward_bn_block")
-            pd = ctx.param_dtypes
-            outs = [t if t.dtype == pd[i] else t.to(pd[i]) for i, t in enumerate((dw, dgam, dbet, dbw, dbb))]
-            o2 = [None, None] if not skip else [t if t.dtype == pd[5 + i] else t.to(pd[5 + i]) for i, t in enumerate((d2w, d2b))]
+            outs = _cast_grads(grads, ctx.param_dtypes)      # (without a skip BatchNorm2d the last two dtypes are None)
             #       conv   identity cfg  g_w      g_gamma  g_beta  g_rm  g_rv  bn_w     bn_b    bn_rm bn_rv eps   mom   nbt   nbt
             return (d_conv, d_idt, None, outs[0], outs[1], outs[2], None, None, outs[3], outs[4], None, None, None, None, None, None,
-                    o2[0], o2[1], None, None, None, None, None)
+                    outs[5], outs[6], None, None, None, None, None)
 
 
-def _glue_cfg(cfg: FusedConfig, need_bwd: bool):
+def _glue_cfg(cfg: FusedConfig, need_bwd: bool, inline: bool = False):
     cb = cfg.content_box if cfg.content_box is not None else (-1, -1, -1, -1)
     sb = cfg.style_box if cfg.style_box is not None else (-1, -1, -1, -1)
     icfg = [int(cfg.cn_active), *(int(v) for v in cb), *(int(v) for v in sb), int(cfg.sn_active), int(cfg.sn_two),
-            int(cfg.sn_training), _strategy, int(need_bwd), _ADD_MODES[cfg.add_mode], int(cfg.relu), 0]
+            int(cfg.sn_training), _strategy, int(need_bwd), _ADD_MODES[cfg.add_mode], int(cfg.relu), int(inline)]
     fcfg = [0.0 if cfg.lam is None else float(cfg.lam), cfg.eps_cn, cfg.eps_sn, cfg.eps_bn, cfg.momentum]
     return icfg, fcfg
 
 
-_tail_plan_cache = {}
-_ffi._plan_caches.append(_tail_plan_cache)
+_tail_plan_cache = _plan_cache()
 
 
 def fused_cnsn_tail(x, cfg: FusedConfig, addend, want_y: bool, g: GateParams, bn_w, bn_b, bn_rm, bn_rv, bn_training: bool,
@@ -799,11 +803,7 @@ def bnrelu_plan_cached(x: torch.Tensor, cfg: FusedConfig, need_bwd: bool) -> boo
     """bnrelu_plan for both directions, remembered per (shape, dtype, configuration, strategy): a per-call ctypes
     round trip is what the fused tail is there to save"""
     key = (tuple(x.shape), x.dtype, x.device.index, cfg.add_mode, cfg.sn_training, cfg.sn_two, _strategy, need_bwd)
-    hit = _tail_plan_cache.get(key)
-    if hit is None:
-        hit = bnrelu_plan(x, cfg) and (not need_bwd or bnrelu_plan(x, cfg, backward=True))
-        _tail_plan_cache[key] = hit
-    return hit
+    return _remembered(_tail_plan_cache, key, lambda: bnrelu_plan(x, cfg) and (not need_bwd or bnrelu_plan(x, cfg, backward=True)))
 
 
 def fused_cnsn(x, cfg: FusedConfig, perm=None, chan_perm=None, g: Optional[GateParams] = None,
@@ -822,12 +822,7 @@ def fused_cnsn(x, cfg: FusedConfig, perm=None, chan_perm=None, g: Optional[GateP
         addend = None
     need_bwd = torch.is_grad_enabled() and (x.requires_grad or any(
         t is not None and t.requires_grad for t in (*ga[:3], *fa[:3], addend)))
-    cb = cfg.content_box if cfg.content_box is not None else (-1, -1, -1, -1)
-    sb = cfg.style_box if cfg.style_box is not None else (-1, -1, -1, -1)
-    inline = cfg.cn_active and perm_inline_ok(x, cfg, perm, chan_perm)
-    icfg = [int(cfg.cn_active), *(int(v) for v in cb), *(int(v) for v in sb), int(cfg.sn_active), int(cfg.sn_two),
-            int(cfg.sn_training), _strategy, int(need_bwd), _ADD_MODES[cfg.add_mode], int(cfg.relu), int(inline)]
-    fcfg = [0.0 if cfg.lam is None else float(cfg.lam), cfg.eps_cn, cfg.eps_sn, cfg.eps_bn, cfg.momentum]
+    icfg, fcfg = _glue_cfg(cfg, need_bwd, cfg.cn_active and perm_inline_ok(x, cfg, perm, chan_perm))
     return glue.fused_cnsn(x, icfg, fcfg, perm if cfg.cn_active else None, chan_perm if cfg.cn_active else None,
                            *ga, *fa, addend, g_nbt, f_nbt)
 
@@ -987,8 +982,7 @@ class InstanceNorm(torch.autograd.Function):
 # Instance-Batch normalisation on channels-last tensors: y = act(Norm(x [+ addend])), InstanceNorm2d on channels [0, half),
 # BatchNorm2d on the rest, ONE launch per direction (cnsn_forward_ibn / cnsn_backward_ibn, csrc/cnsn_nhwc_ibn_kernels.h)
 # ------------------------------------------------------------------------------------------------
-_ibn_plan_cache = {}
-_ffi._plan_caches.append(_ibn_plan_cache)
+_ibn_plan_cache = _plan_cache()
 
 
 def _ibn_desc(x: torch.Tensor, half: int, relu: bool, eps_in: float, in_w=None, in_b=None, bn: Optional[_ffi.BnTail] = None):
@@ -1010,21 +1004,15 @@ def ibn_plan(x: torch.Tensor, half: int, relu: bool = True, has_addend: bool = F
     channels-last, fp32 / bf16 / f16, C and half multiples of 8, 2 <= N <= 256, H*W >= 2, no unforgiven time-out, CNSN_NHWC_FUSED
     not 0) — and never while the stream is being captured into a graph (as `bn_block_plan`).  Remembered per (shape, dtype,
     configuration)."""
-    if not x.is_cuda or x.dim() != 4 or x.dtype not in _DTYPES or torch.cuda.is_current_stream_capturing():
+    if not _single_launch_tensor(x) or torch.cuda.is_current_stream_capturing():     # (degraded: today's path)
         return False
-    if not x.is_contiguous(memory_format=torch.channels_last) or x.is_contiguous():
-        return False
-    if _ffi.lib().cnsn_resident_degraded():      # (a persistent launch gave up and nobody re-armed since: today's path)
-        return False
-    key = (tuple(x.shape), x.dtype, x.device.index, int(half), bool(relu), bool(has_addend), bool(bn_training))
-    hit = _ibn_plan_cache.get(key)
-    if hit is None:
+
+    def ask():
         d = _ibn_desc(x, half, relu, 1e-5)
         d.bn.training = int(bool(bn_training))
-        lib = _ffi.lib()
-        hit = lib.cnsn_ibn_plan(C.byref(d), int(has_addend), 0) == 1 and lib.cnsn_ibn_plan(C.byref(d), int(has_addend), 1) == 1
-        _ibn_plan_cache[key] = hit
-    return hit
+        return all(_ffi.lib().cnsn_ibn_plan(C.byref(d), int(has_addend), back) == 1 for back in (0, 1))
+    key = (tuple(x.shape), x.dtype, x.device.index, int(half), bool(relu), bool(has_addend), bool(bn_training))
+    return _remembered(_ibn_plan_cache, key, ask)
 
 
 class IBNorm(torch.autograd.Function):
@@ -1042,34 +1030,24 @@ class IBNorm(torch.autograd.Function):
         with torch.cuda.device(x.device):
             lib = _ffi.lib()
             _ffi.check_resident_health("cnsn_forward_ibn")
-            x = _dense_cl(x)
-            if addend is not None:
-                _require_device(addend, "cnsn_forward_ibn(addend)")
-                assert addend.shape == x.shape and addend.dtype == x.dtype, "addend must match x"
-                addend = _dense_cl(addend)
+            x, addend = _cl_inputs(x, addend, "cnsn_forward_ibn")
             dev = x.device
-            n, c = int(x.shape[0]), int(x.shape[1])
             iw = _f32(in_w) if in_w is not None else None
             ib = _f32(in_b) if in_b is not None else None
-            bn, bw, bb = None, None, None
-            if half < c:
-                bw, bb = _f32(bn_w), _f32(bn_b)
-                bn = _ffi.BnTail(C.sizeof(_ffi.BnTail), int(bool(bn_training)), float(bn_eps), float(bn_momentum), bw.data_ptr(),
-                                 bb.data_ptr(), bn_rm.data_ptr(), bn_rv.data_ptr(), _ptr(bn_nbt))
-            d = _ibn_desc(x, half, relu, eps_in, iw, ib, bn)
-            prob = _problem(x, FusedConfig(sn_active=True))      # (the persistent context of the single-launch kernels)
-            prob.layout = _ffi.LAYOUT_NHWC
-            _context(prob, dev)
-            d.context, d.context_bytes = prob.context, prob.context_bytes
+            bn = _Bn2dBuffers(bn_w, bn_b, bn_rm, bn_rv, bn_eps, bn_momentum, bn_nbt, bn_training) if half < x.shape[1] else None
+            d = _ibn_desc(x, half, relu, eps_in, iw, ib, bn.c if bn else None)
+            d.context, d.context_bytes = _nhwc_context(x)
             need_bwd = any(ctx.needs_input_grad)
             saved = torch.empty(lib.cnsn_ibn_saved_floats(C.byref(d)), dtype=torch.float32, device=dev) if need_bwd else None
             ws_bytes = lib.cnsn_ibn_workspace_bytes(C.byref(d))
-            ws = torch.empty(ws_bytes // 4 + 4, dtype=torch.float32, device=dev)
+            ws = _workspace(ws_bytes, dev)
             y = _out_like(x)
             st = lib.cnsn_forward_ibn(C.byref(d), _ptr(x), _ptr(addend), _ptr(y), _ptr(saved), _ptr(ws), ws_bytes, _stream(x))
             _ffi.check(st, "cnsn_forward_ibn")
+            if bn:
+                bn.write_back()
             if need_bwd:
-                ctx.desc, ctx.prob, ctx.keep = d, prob, (iw, ib, bw, bb)   # (the descriptor points at them)
+                ctx.desc, ctx.keep = d, (iw, ib, bn)               # (the descriptor points at them)
                 ctx.has_addend = addend is not None
                 ctx.param_dtypes = tuple(t.dtype if t is not None else None for t in (in_w, in_b, bn_w, bn_b))
                 ctx.save_for_backward(x, addend, saved)
@@ -1083,24 +1061,20 @@ class IBNorm(torch.autograd.Function):
             d = ctx.desc
             dev = x.device
             c, half = int(x.shape[1]), int(d.half)
-            gy = _dense_cl(gy if gy.dtype == x.dtype else gy.to(x.dtype))
-            prob = ctx.prob
-            _context(prob, dev)                                  # (the context in force now, as the other backwards take it)
-            d.context, d.context_bytes = prob.context, prob.context_bytes
-            if torch.cuda.is_current_stream_capturing():
-                d.context, d.context_bytes = None, 0
+            gy = _grad_like(gy, x, True)
+            d.context, d.context_bytes = _nhwc_context(x)        # (the context in force now, as the other backwards take it)
             dx = _out_like(x)
             flat = torch.empty(2 * c, dtype=torch.float32, device=dev)
             diw, dib, dbw, dbb = flat[:half], flat[half:2 * half], flat[2 * half:c + half], flat[c + half:]
             pd = ctx.param_dtypes
             ws_bytes = lib.cnsn_ibn_workspace_bytes(C.byref(d))
-            ws = torch.empty(ws_bytes // 4 + 4, dtype=torch.float32, device=dev)
+            ws = _workspace(ws_bytes, dev)
             st = lib.cnsn_backward_ibn(C.byref(d), _ptr(gy), _ptr(x), _ptr(addend), _ptr(saved), _ptr(dx),
                                        _ptr(diw) if pd[0] is not None else None, _ptr(dib) if pd[1] is not None else None,
                                        _ptr(dbw) if pd[2] is not None else None, _ptr(dbb) if pd[3] is not None else None,
                                        _ptr(ws), ws_bytes, _stream(x))
             _ffi.check(st, "cnsn_backward_ibn")           # (never declines the record of its own forward: cnsn_nhwc_ibn.hip)
-            grads = [None if pd[i] is None else (t if t.dtype == pd[i] else t.to(pd[i])) for i, t in enumerate((diw, dib, dbw, dbb))]
+            grads = _cast_grads((diw, dib, dbw, dbb), pd)
             #       x   addend                          in_w      in_b      bn_w      bn_b      rm    rv    half  relu  eps   tr    eps   mom   nbt
             return (dx, dx if ctx.has_addend else None, grads[0], grads[1], grads[2], grads[3], None, None, None, None, None, None, None,
                     None, None)
@@ -1110,8 +1084,7 @@ class IBNorm(torch.autograd.Function):
 # BatchNorm2d (+ add) + ReLU on channels-last tensors: y = act(BatchNorm2d(x) [+ addend]), ONE launch per direction in training
 # mode, one plain launch in eval mode (cnsn_forward_bn_act / cnsn_backward_bn_act, csrc/cnsn_nhwc_bn_kernels.h)
 # ------------------------------------------------------------------------------------------------
-_bn_act_plan_cache = {}
-_ffi._plan_caches.append(_bn_act_plan_cache)
+_bn_act_plan_cache = _plan_cache()
 
 
 def _bn_act_desc(x: torch.Tensor, relu: bool, has_addend: bool, bn: Optional[_ffi.BnTail] = None, training: bool = True):
@@ -1134,22 +1107,13 @@ def bn_act_plan(x: torch.Tensor, relu: bool = True, has_addend: bool = False, tr
     directions of the single launch (at least 8 tiles of 64 rows; no unforgiven time-out, `set_resident` / CNSN_RESIDENT and
     CNSN_NHWC_FUSED as for the other single launches).  Eval mode: the plain forward launch (no backward: the caller keeps
     today's path when a gradient is needed).  Remembered per (shape, dtype, configuration)."""
-    if not x.is_cuda or x.dim() != 4 or x.dtype not in _DTYPES:
+    if not _single_launch_tensor(x, poll=training):           # (the eval launch has no barrier: a time-out does not bear on it)
         return False
-    if not x.is_contiguous(memory_format=torch.channels_last) or x.is_contiguous():
-        return False
-    if training and _ffi.lib().cnsn_resident_degraded():      # (a persistent launch gave up and nobody re-armed since)
-        return False
-    key = (tuple(x.shape), x.dtype, x.device.index, bool(relu), bool(has_addend), bool(training))
-    hit = _bn_act_plan_cache.get(key)
-    if hit is None:
+
+    def ask():
         d = _bn_act_desc(x, relu, has_addend, training=training)
-        lib = _ffi.lib()
-        hit = lib.cnsn_bn_act_plan(C.byref(d), int(has_addend), 0) == 1
-        if training:
-            hit = hit and lib.cnsn_bn_act_plan(C.byref(d), int(has_addend), 1) == 1
-        _bn_act_plan_cache[key] = hit
-    return hit
+        return all(_ffi.lib().cnsn_bn_act_plan(C.byref(d), int(has_addend), back) == 1 for back in ((0, 1) if training else (0,)))
+    return _remembered(_bn_act_plan_cache, (tuple(x.shape), x.dtype, x.device.index, bool(relu), bool(has_addend), bool(training)), ask)
 
 
 class BatchNormAct(torch.autograd.Function):
@@ -1167,34 +1131,24 @@ class BatchNormAct(torch.autograd.Function):
             lib = _ffi.lib()
             if training:
                 _ffi.check_resident_health("cnsn_forward_bn_act")
-            x = _dense_cl(x)
-            if addend is not None:
-                _require_device(addend, "cnsn_forward_bn_act(addend)")
-                assert addend.shape == x.shape and addend.dtype == x.dtype, "addend must match x"
-                addend = _dense_cl(addend)
+            x, addend = _cl_inputs(x, addend, "cnsn_forward_bn_act")
             dev = x.device
-            bn = _Bn2dBuffers(bn_w, bn_b, bn_rm, bn_rv, bn_eps, bn_momentum, bn_nbt if training else None)
-            bn.c.training = int(bool(training))
+            bn = _Bn2dBuffers(bn_w, bn_b, bn_rm, bn_rv, bn_eps, bn_momentum, bn_nbt, training)
             d = _bn_act_desc(x, relu, addend is not None, bn.c, training)
             need_bwd = bool(training) and any(ctx.needs_input_grad)    # (eval: forward only — callers.bn_act keeps torch's path
-            prob = None                                                #  when a gradient is needed; the output carries none)
-            if training:
-                prob = _problem(x, FusedConfig(sn_active=True))      # (the persistent context of the single-launch kernels)
-                prob.layout = _ffi.LAYOUT_NHWC
-                _context(prob, dev)
-                d.context, d.context_bytes = prob.context, prob.context_bytes
+            if training:                                               #  when a gradient is needed; the output carries none)
+                d.context, d.context_bytes = _nhwc_context(x)
             saved = torch.empty(lib.cnsn_bn_act_saved_floats(C.byref(d)), dtype=torch.float32, device=dev) if need_bwd else None
             ws_bytes = lib.cnsn_bn_act_workspace_bytes(C.byref(d))
-            ws = torch.empty(ws_bytes // 4 + 4, dtype=torch.float32, device=dev)
+            ws = _workspace(ws_bytes, dev)
             y = _out_like(x)
             st = lib.cnsn_forward_bn_act(C.byref(d), _ptr(x), _ptr(addend), _ptr(y), _ptr(saved), _ptr(ws), ws_bytes, _stream(x))
             _ffi.check(st, "cnsn_forward_bn_act")
-            if training:
-                bn.write_back()
-            else:
+            bn.write_back()
+            if not training:
                 ctx.mark_non_differentiable(y)
             if need_bwd:
-                ctx.desc, ctx.prob, ctx.keep = d, prob, bn           # (the descriptor points at the float32 parameters)
+                ctx.desc, ctx.keep = d, bn                         # (the descriptor points at the float32 parameters)
                 ctx.has_addend, ctx.relu = addend is not None, bool(relu)
                 ctx.param_dtypes = (bn_w.dtype, bn_b.dtype)
                 ctx.save_for_backward(x, addend if relu else None, saved)
@@ -1208,25 +1162,19 @@ class BatchNormAct(torch.autograd.Function):
             d = ctx.desc
             dev = x.device
             c = int(x.shape[1])
-            gy = _dense_cl(gy if gy.dtype == x.dtype else gy.to(x.dtype))
-            prob = ctx.prob
-            _context(prob, dev)                                  # (the context in force now, as the other backwards take it)
-            d.context, d.context_bytes = prob.context, prob.context_bytes
-            if torch.cuda.is_current_stream_capturing():
-                d.context, d.context_bytes = None, 0
+            gy = _grad_like(gy, x, True)
+            d.context, d.context_bytes = _nhwc_context(x)        # (the context in force now, as the other backwards take it)
             dx = _out_like(x)
             da = _out_like(x) if addend is not None else None    # (ReLU behind the addend: the masked gradient)
-            flat = torch.empty(2 * c, dtype=torch.float32, device=dev)
-            dw, db = flat[:c], flat[c:]
+            dw, db = torch.empty(2 * c, dtype=torch.float32, device=dev).view(2, c).unbind(0)
             ws_bytes = lib.cnsn_bn_act_workspace_bytes(C.byref(d))
-            ws = torch.empty(ws_bytes // 4 + 4, dtype=torch.float32, device=dev)
+            ws = _workspace(ws_bytes, dev)
             st = lib.cnsn_backward_bn_act(C.byref(d), _ptr(gy), _ptr(x), _ptr(addend), _ptr(saved), _ptr(dx), _ptr(da), _ptr(dw),
                                           _ptr(db), _ptr(ws), ws_bytes, _stream(x))
             _ffi.check(st, "cnsn_backward_bn_act")        # (never declines the record of its own forward: cnsn_nhwc_bn.hip)
             if ctx.has_addend and da is None:
                 da = gy                                          # (no ReLU: the addend's gradient is grad_y itself)
-            pd = ctx.param_dtypes
-            dw, db = (dw if pd[0] == torch.float32 else dw.to(pd[0])), (db if pd[1] == torch.float32 else db.to(pd[1]))
+            dw, db = _cast_grads((dw, db), ctx.param_dtypes)
             #       x   addend                          w   b   rm    rv    relu  train eps   mom   nbt
             return dx, (da if ctx.has_addend else None), dw, db, None, None, None, None, None, None, None
 

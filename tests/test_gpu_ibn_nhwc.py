@@ -312,3 +312,38 @@ def test_bf16_autocast_fused_against_unfused(shape, half):
     assert cosd(y_f, y_p) <= 1e-4
     for i, (a, b) in enumerate(zip(g_f, g_p)):
         assert cosd(a, b) <= 1e-3, f"gradient {i}: cosine distance {cosd(a, b):.2e}"
+
+
+def test_running_buffers_in_bf16_and_a_host_counter_go_through_the_marshal():
+    """functional.IBNorm called directly (no callers._fusable in front) with the BatchNorm2d's running buffers held in bf16 and
+    its counter on the host: the one BatchNorm2d marshal (functional._Bn2dBuffers) hands the kernel float32 copies, writes the
+    update back rounded, and counts on the host — y, dx and the four parameter gradients are bit-identical to the run with float32
+    buffers and a device counter, the bf16 buffers are that run's rounded to bf16, both counters read 1."""
+    n, c, h, w, half = 8, 32, 6, 6, 16
+    gen = torch.Generator().manual_seed(21)
+    x0 = (torch.randn(n, c, h, w, generator=gen) * 1.5).to(DEV, torch.bfloat16).contiguous(memory_format=CL)
+    gy = torch.randn(n, c, h, w, generator=gen).to(DEV, torch.bfloat16).contiguous(memory_format=CL)
+    assert functional.ibn_plan(x0, half, relu=True, has_addend=False, bn_training=True)
+    start = [torch.rand(half, generator=gen) + 0.5, torch.randn(half, generator=gen),          # in_w, in_b
+             torch.rand(c - half, generator=gen) + 0.5, torch.randn(c - half, generator=gen),  # bn_w, bn_b
+             torch.randn(c - half, generator=gen) * 0.1, torch.rand(c - half, generator=gen) + 0.5]   # running mean / var
+    start[4], start[5] = start[4].bfloat16().float(), start[5].bfloat16().float()             # (equal values in either dtype)
+
+    def run(buf_dtype, counter_dev):
+        params = [t.clone().to(DEV).requires_grad_() for t in start[:4]]
+        rm, rv = start[4].to(DEV, buf_dtype), start[5].to(DEV, buf_dtype)
+        nbt = torch.zeros((), dtype=torch.int64, device=counter_dev)
+        x = x0.clone().requires_grad_()
+        y = functional.IBNorm.apply(x, None, *params, rm, rv, half, True, 1e-5, True, 1e-5, 0.1, nbt)
+        y.backward(gy)
+        torch.cuda.synchronize()
+        return [y.detach(), x.grad, *(p.grad for p in params)], rm, rv, nbt
+
+    want, rm32, rv32, nbt32 = run(torch.float32, DEV)
+    got, rm16, rv16, nbt16 = run(torch.bfloat16, "cpu")
+    for name, u, v in zip(("y", "dx", "d_in_w", "d_in_b", "d_bn_w", "d_bn_b"), got, want):
+        assert u.dtype == v.dtype and torch.equal(u, v), name
+    assert rm16.dtype == rv16.dtype == torch.bfloat16
+    assert torch.equal(rm16, rm32.bfloat16()) and torch.equal(rv16, rv32.bfloat16())
+    assert not torch.equal(rm32, start[4].to(DEV)) and not torch.equal(rv32, start[5].to(DEV))   # (the launch did update them)
+    assert int(nbt32) == 1 and int(nbt16) == 1 and not nbt16.is_cuda
