@@ -128,6 +128,7 @@ int bn_act_forward(const cnsn_bn_act_t& d, const void* x, const void* addend, vo
     if (saved) a.stat = saved;  // (written through: the backward's launch reads it like any other memory)
     a.keep = keep_first_read(1, tensor_bytes(d));  // (the addend is read once, in phase C)
     const cnsn_problem_t pr = context_of(d);
+    int grid = 0;
     dispatch_t(d.dtype, [&](auto tt, auto vt) {
         using T = typename decltype(tt)::type;
         constexpr int VEC = decltype(vt)::value;
@@ -135,15 +136,15 @@ int bn_act_forward(const cnsn_bn_act_t& d, const void* x, const void* addend, vo
         with_flag(addend != nullptr, [&](auto at) {
             constexpr bool ADD = decltype(at)::value;
             auto go = [&](auto kern) {
-                status = launch_coresident(pr, kern, lds, a, a.bar, a.ntiles, w.bar, stream, (const T*)x,
+                status = launch_coresident(pr, kern, lds, a, a.bar, a.ntiles, w.bar, stream, &grid, (const T*)x,
                                            (const T*)addend, (T*)y);
             };
             a.keep ? go(nhwc_bnact_fwd_kernel<T, VEC, ADD, true>) : go(nhwc_bnact_fwd_kernel<T, VEC, ADD, false>);
         });
     });
     if (knob(K_DEBUG))
-        fprintf(stderr, "[cnsn] nhwc bn_act fwd: R=%d C=%d tiles=%d (ncb=%d tcb=%d rows=%d chunk=%d) keep=%d -> status %d\n", g.R, g.C,
-                a.ntiles, g.ncb, g.tcb, g.rows, g.chunk, a.keep, status);
+        fprintf(stderr, "[cnsn] nhwc bn_act fwd: R=%d C=%d tiles=%d (ncb=%d tcb=%d rows=%d chunk=%d) keep=%d -> status %d grid=%d\n", g.R,
+                g.C, a.ntiles, g.ncb, g.tcb, g.rows, g.chunk, a.keep, status, grid);
     return status;
 }
 
@@ -160,7 +161,7 @@ int bn_act_backward(const cnsn_bn_act_t& d, const void* gy, const void* x, const
     const cnsn_problem_t pr = context_of(d);
     // launch_coresident cannot decline a call bn_act_ok accepts: the grid is occupancy (>= 1: no scratch, 128 VGPRs) x at least
     // 8 compute units, a multiple of 8 and at most the tiles, which are >= 8 here
-    int status = CNSN_E_UNSUPPORTED;
+    int status = CNSN_E_UNSUPPORTED, grid = 0;
     dispatch_t(d.dtype, [&](auto tt, auto vt) {
         using T = typename decltype(tt)::type;
         constexpr int VEC = decltype(vt)::value;
@@ -168,15 +169,15 @@ int bn_act_backward(const cnsn_bn_act_t& d, const void* gy, const void* x, const
         with_flag(add, [&](auto at) {
             constexpr bool ADD = decltype(at)::value;
             auto go = [&](auto kern) {
-                status = launch_coresident(pr, kern, lds, a, a.bar, a.ntiles, w.bar, stream, (const T*)gy, (const T*)x,
-                                           (const T*)addend, (T*)dx, (T*)d_addend);
+                status = launch_coresident(pr, kern, lds, a, a.bar, a.ntiles, w.bar, stream, &grid, (const T*)gy,
+                                           (const T*)x, (const T*)addend, (T*)dx, (T*)d_addend);
             };
             a.keep ? go(nhwc_bnact_bwd_kernel<T, VEC, ADD, true>) : go(nhwc_bnact_bwd_kernel<T, VEC, ADD, false>);
         });
     });
     if (knob(K_DEBUG))
-        fprintf(stderr, "[cnsn] nhwc bn_act bwd: R=%d C=%d tiles=%d (ncb=%d tcb=%d rows=%d chunk=%d) keep=%d -> status %d\n", g.R, g.C,
-                a.ntiles, g.ncb, g.tcb, g.rows, g.chunk, a.keep, status);
+        fprintf(stderr, "[cnsn] nhwc bn_act bwd: R=%d C=%d tiles=%d (ncb=%d tcb=%d rows=%d chunk=%d) keep=%d -> status %d grid=%d\n", g.R,
+                g.C, a.ntiles, g.ncb, g.tcb, g.rows, g.chunk, a.keep, status, grid);
     return status;
 }
 

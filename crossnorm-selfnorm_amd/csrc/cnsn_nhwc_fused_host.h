@@ -87,11 +87,13 @@ inline NhwcFusedArgs make_args(const Plan& pl, const NhwcGeom& ng, int relu, int
 }
 
 // issue `kern` with a co-resident grid (a multiple of 8: the barrier's groups are equal) of at most `ntiles` workgroups; the two
-// barriers are booked on the context before the launch.  `a`: the kernel's first argument, `bar` the GridBar inside it
+// barriers are booked on the context before the launch.  `a`: the kernel's first argument, `bar` the GridBar inside it;
+// `grid_out` (may be null): the grid that was chosen, for the caller's debug line
 template <typename A, typename Kern, typename... Args>
 int launch_coresident(const cnsn_problem_t& pr, Kern kern, size_t lds, A& a, GridBar& bar, int ntiles, void* ws_bar,
-                      hipStream_t stream, Args... args) {
+                      hipStream_t stream, int* grid_out, Args... args) {
     const int grid = reshost::grid_for(kern, lds, 8, ntiles & ~7);
+    if (grid_out) *grid_out = grid;
     if (grid < 8) return CNSN_E_UNSUPPORTED;
     ResidentChain chain(stream);  // persistent grids of different streams never overlap
     const BarArea ba = resident_bar_area(pr, ws_bar, stream, grid, 2);
@@ -110,7 +112,7 @@ int launch_coresident(const cnsn_problem_t& pr, Kern kern, size_t lds, A& a, Gri
 // ... for the kernels whose first argument is, or holds, a NhwcFusedArgs (`fa`)
 template <typename A, typename Kern, typename... Args>
 int launch_fused(const Plan& pl, Kern kern, size_t lds, A& a, NhwcFusedArgs& fa, void* ws_bar, hipStream_t stream, Args... args) {
-    return launch_coresident(pl.pr, kern, lds, a, fa.bar, fa.ntiles, ws_bar, stream, args...);
+    return launch_coresident(pl.pr, kern, lds, a, fa.bar, fa.ntiles, ws_bar, stream, (int*)nullptr, args...);
 }
 
 }  // namespace nhwc_host

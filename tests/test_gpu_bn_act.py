@@ -90,9 +90,12 @@ def compare(name, got, t64, t32, dtype, param=False):
 
 
 def run_case(shape, dtype, relu=True, addend=False, training=True, momentum=0.1, special=False, seed=0, expect_fused=True,
-             gen_dev="cpu"):
+             gen_dev="cpu", edit=None, out=None):
     """special: channel 0 is constant (variance 0), channel 1 has a mean 1 000 x its standard deviation.  gen_dev: where the
-    inputs are drawn and the float64 reference runs (the full-size cases: the GPU, one case at a time)."""
+    inputs are drawn and the float64 reference runs (the full-size cases: the GPU, one case at a time).  edit(bn, x64, a64):
+    changes the module's parameters and the drawn inputs in place before anything reads them (test_gpu_bn_act_geometry.py:
+    channels with weight 0).  out: a dict that receives the device's tensors, the gradient it was given and the two references.
+    Returns {tensor: (err, bound)} of everything compared."""
     n, c, h, w = shape
     gen = torch.Generator(device=gen_dev).manual_seed(seed)
 
@@ -105,6 +108,9 @@ def run_case(shape, dtype, relu=True, addend=False, training=True, momentum=0.1,
     a64 = draw(*shape) if addend else None
     gy64 = draw(*shape) if training else None
     bn = make_bn(c, momentum, seed).train(training)
+    if edit is not None:
+        with torch.no_grad():
+            edit(bn, x64, a64)
     state = {k: v.clone() for k, v in bn.state_dict().items()}
     dbn = bn.to(DEV)
     xs, as_ = x64.to(dtype), (a64.to(dtype) if addend else None)                  # (the values the device sees)
@@ -128,13 +134,17 @@ def run_case(shape, dtype, relu=True, addend=False, training=True, momentum=0.1,
         pre64, pre32 = pre64.clamp_min(0), pre32.clamp_min(0)
     margins = {"y": compare("y", y, pre64, pre32, dtype)}
     if training:
-        compare("dx", xg.grad, r64[1], r32[1], dtype)
+        margins["dx"] = compare("dx", xg.grad, r64[1], r32[1], dtype)
         assert xg.grad.is_contiguous(memory_format=CL) and xg.grad.dtype == dtype
         if addend:
-            compare("d_addend", ag.grad, r64[2], r32[2], dtype)
-        compare("d_weight", dbn.weight.grad, r64[3], r32[3], dtype, param=True)
-        compare("d_bias", dbn.bias.grad, r64[4], r32[4], dtype, param=True)
+            margins["d_addend"] = compare("d_addend", ag.grad, r64[2], r32[2], dtype)
+        margins["d_weight"] = compare("d_weight", dbn.weight.grad, r64[3], r32[3], dtype, param=True)
+        margins["d_bias"] = compare("d_bias", dbn.bias.grad, r64[4], r32[4], dtype, param=True)
     st = dbn.state_dict()
+    if out is not None:
+        out.update(y=y.detach(), dx=xg.grad, d_addend=ag.grad if addend else None, d_weight=dbn.weight.grad, d_bias=dbn.bias.grad,
+                   running_mean=st["running_mean"], running_var=st["running_var"], gy=gy64.to(dtype) if training else None,
+                   ref64=r64, ref32=r32)
     assert int(st["num_batches_tracked"]) == int(r64[5]["num_batches_tracked"]) == (4 if training else 3)
     for k in ("running_mean", "running_var"):
         t64 = r64[5][k].double().cpu()
@@ -142,6 +152,7 @@ def run_case(shape, dtype, relu=True, addend=False, training=True, momentum=0.1,
         bound = (1e-5 if dtype == torch.float32 else 1e-2) * max(1.0, float(t64.abs().max()))
         print(f"    {k}: err {err:.3e} bound {bound:.3e}")
         assert err <= bound, f"{k}: err {err:.3e}"
+        margins[k] = (err, bound)
     return margins
 
 
