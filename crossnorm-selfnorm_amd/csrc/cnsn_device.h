@@ -210,4 +210,25 @@ struct Geom {
                // finds them in L2 / the Infinity Cache); 0 = non-temporal like every other plane access
 };
 
+// ------------------------------------------------------------------------------------------------
+// the shift of the one-pass sums
+// ------------------------------------------------------------------------------------------------
+// Every kernel that takes first and second moments in ONE pass sums d = X - K and d^2 in float about a shift K read from the
+// tensor itself, so that S2 - S1^2/M does not cancel when |mean| >> std.  Those float sums lose about ((K - mean)/std)^2 * 2^-24
+// of the variance, so K has to be TYPICAL of its plane.  One sample is not: pixel (0, 0) is the most atypical pixel a
+// zero-padded convolution writes.  K is the MEDIAN of three samples on the plane's diagonal, a quarter, a half and three
+// quarters of the way along both axes and never on the border of a plane that has an interior: no single pixel and no set of
+// border pixels can move it (tests/test_gpu_shift_sample.py).  Every workgroup reads the samples for itself.
+__host__ __device__ inline int shift_sample_coord(int size, int i) {
+    int v = (i + 1) * size / 4;
+    if (v > size - 2) v = size - 2;
+    if (v < 1) v = 1;
+    return v < size ? v : size - 1;
+}
+// pixel (< H*W) of sample i = 0, 1, 2
+__host__ __device__ inline int shift_sample_pixel(int H, int W, int i) {
+    return shift_sample_coord(H, i) * W + shift_sample_coord(W, i);
+}
+__device__ __forceinline__ float median3(float a, float b, float c) { return fmaxf(fminf(a, b), fminf(fmaxf(a, b), c)); }
+
 }  // namespace cnsn

@@ -85,13 +85,13 @@ __global__ __launch_bounds__(kBlock) void fused_stats_kernel(const T* __restrict
     __shared__ float lds[4 * NACC];
     const PlaneId<LPP> id(g.P);
     const size_t off = (size_t)id.p * g.M;
-    float K = 0.f;
-    {
-        const Vec<T, VEC> fa = load_vec<T, VEC>(x + off), fb = load_vec<T, VEC>(addend + off);
+    const float K = plane_shift<VEC>(g, [&](size_t e) {
+        const Vec<T, VEC> fa = load_vec<T, VEC>(x + off + e), fb = load_vec<T, VEC>(addend + off + e);
+        float m = 0.f;
 #pragma unroll
-        for (int j = 0; j < VEC; ++j) K += sum_t<T>(to_float(fa.v[j]), to_float(fb.v[j]));
-        K *= (1.0f / VEC);
-    }
+        for (int j = 0; j < VEC; ++j) m += sum_t<T>(to_float(fa.v[j]), to_float(fb.v[j]));
+        return m * (1.0f / VEC);
+    });
     float part[NACC][VEC];
 #pragma unroll
     for (int k = 0; k < NACC; ++k)

@@ -44,6 +44,11 @@ BnActGeom bn_act_geom(const cnsn_bn_act_t& d, bool eval = false) {
         g.chunk = (int)((g.R + want - 1) / want);
     }
     g.wpc = (g.R + g.chunk - 1) / g.chunk;
+    // the shift's samples: a pixel inside the plane of the images a quarter, a half and three quarters through the batch
+    for (int i = 0; i < 3; ++i) {
+        const int n = (i + 1) * d.N / 4 < d.N ? (i + 1) * d.N / 4 : d.N - 1;
+        g.ks[i] = n * d.H * d.W + shift_sample_pixel(d.H, d.W, i);
+    }
     return g;
 }
 

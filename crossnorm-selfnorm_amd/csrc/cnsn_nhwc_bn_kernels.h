@@ -7,9 +7,11 @@
 // sums — and with them every result — do not depend on how many workgroups the grid got.  With a grid that is a multiple of the
 // column blocks (1, 2, 4 or 8 for every width of a ResNet; the grid is a multiple of 8) a workgroup's tiles share a column block.
 // A thread owns VEC adjacent channels of a row and walks `rows` apart: statistics are in-lane column sums.
-//   A  every tile: sum(x - k_c) and sum((x - k_c)^2) over its rows, k_c = x[row 0, c] — a shift every workgroup reads for
-//      itself, so the tiles' sums merge by plain addition (in double): no Chan merge, no shift array.  Rows merged in LDS, ONE
-//      16-byte write-through record per tile and four channels: side traffic tiles x 2 x C/ncb floats
+//   A  every tile: sum(x - k_c) and sum((x - k_c)^2) over its rows, k_c = the median of x[row, c] over three rows
+//      (BnActGeom::ks: a pixel inside the plane of three images spread over the batch — the shift of cnsn_device.h; no border
+//      pixel and no single image can make it atypical) — a shift every workgroup reads for itself, so the tiles' sums merge by
+//      plain addition (in double): no Chan merge, no shift array.  Rows merged in LDS, ONE 16-byte write-through record per
+//      tile and four channels: side traffic tiles x 2 x C/ncb floats
 //   -- barrier --
 //   B  a workgroup per four adjacent channels: the tiles' sums added in double -> mean, BIASED variance, rstd; running_mean,
 //      running_var (unbiased, momentum as given), num_batches_tracked += 1; mean and rstd written through (to `saved` when the
@@ -49,6 +51,7 @@ struct BnActGeom {
     int ncb;      // column blocks
     int wpc;      // row chunks (tiles per column block)
     int chunk;    // rows per chunk (the last one may be shorter, none is empty)
+    int ks[3];    // the rows the shift of the sums is the median of
 };
 
 struct BnActArgs {
@@ -112,6 +115,13 @@ __device__ __forceinline__ void bn_act_rows_sum(const BnActGeom& g, const BnActT
     __syncthreads();  // (the staging area is the next tile's)
 }
 
+// the shift of channel c (phase A: per vector; phase B: per channel)
+template <typename T>
+__device__ __forceinline__ float bn_act_shift(const BnActGeom& g, const T* __restrict__ x, int c) {
+    return median3(to_float(x[(size_t)g.ks[0] * g.C + c]), to_float(x[(size_t)g.ks[1] * g.C + c]),
+                   to_float(x[(size_t)g.ks[2] * g.C + c]));
+}
+
 // phase B / B': the tiles' two sums of four adjacent channels, added over the tiles in double by the whole workgroup
 __device__ __forceinline__ void bn_act_gather(const BnActArgs& a, int c0, double (&acc)[8], double* red) {
     const BnActGeom& g = a.g;
@@ -172,16 +182,17 @@ __global__ __launch_bounds__(kBlock, CNSN_NHWC_WG_PER_CU) void nhwc_bnact_fwd_ke
     __shared__ int bar_flag;
     const BnActGeom& g = a.g;
 
-    // ---- A: the two sums of every tile about row 0
+    // ---- A: the two sums of every tile about the channels' shift
     for (int tile = blockIdx.x; tile < a.ntiles; tile += gridDim.x) {
         const BnActTile<VEC> t(g, tile);
         float K[VEC], acc[2][VEC];
 #pragma unroll
         for (int j = 0; j < VEC; ++j) K[j] = acc[0][j] = acc[1][j] = 0.f;
         if (t.active) {
-            const Vec<T, VEC> v0 = load_vec<T, VEC>(x + t.elem(g, 0));
+            const Vec<T, VEC> k0 = load_vec<T, VEC>(x + t.elem(g, g.ks[0])), k1 = load_vec<T, VEC>(x + t.elem(g, g.ks[1])),
+                              k2 = load_vec<T, VEC>(x + t.elem(g, g.ks[2]));
 #pragma unroll
-            for (int j = 0; j < VEC; ++j) K[j] = to_float(v0.v[j]);
+            for (int j = 0; j < VEC; ++j) K[j] = median3(to_float(k0.v[j]), to_float(k1.v[j]), to_float(k2.v[j]));
             auto eat = [&](const Vec<T, VEC>& va) {
 #pragma unroll
                 for (int j = 0; j < VEC; ++j) {
@@ -220,7 +231,7 @@ __global__ __launch_bounds__(kBlock, CNSN_NHWC_WG_PER_CU) void nhwc_bnact_fwd_ke
             for (int q = 0; q < 4; ++q) {
                 const int c = c0 + q;
                 const double s1 = acc[q], s2 = acc[4 + q];
-                const double mean = (double)to_float(x[c]) + s1 * a.inv_r;
+                const double mean = (double)bn_act_shift<T>(g, x, c) + s1 * a.inv_r;
                 const double m2 = s2 - s1 * s1 * a.inv_r;
                 const double var = (m2 > 0.0 ? m2 : 0.0) * a.inv_r;  // biased: what normalises (torch)
                 const double rstd = 1.0 / sqrt(var + (double)a.bn.eps);

@@ -7,7 +7,7 @@
 // (MIOpen: 6 ms forward + 9 ms backward of a 44 ms step, profiles/r06e_resnet50_channels_last_step_kernel_stats.csv), and the
 // 16 bn3 layers — the block's widest tensors — are half of that.  Un-fused, a block's tail moves 18 tensor passes per step:
 // BatchNorm2d 3 + 5 (statistics, normalise; two reductions, apply), the op 5 + 5 (cnsn_nhwc_fused_kernels.h).  Here 13:
-//   forward   A  read conv_out, identity: per-plane sums of c, c^2, b, b^2, c*b (about the plane's first pixel)
+//   forward   A  read conv_out, identity: per-plane sums of c, c^2, b, b^2, c*b (about either tensor's shift: nhwc_shift)
 //             B  BatchNorm2d's batch statistics from the plane sums (Chan merge over the batch) -> alpha, beta per channel;
 //                the statistics of X = alpha*c + beta + b per plane BY ALGEBRA (mean, M2 from the five sums) -> SelfNorm's gate
 //             C  read conv_out, identity again: x = T(alpha*c + beta), X = T(x + b), y = act(g * X)          (2 + 2 + 1 passes)
@@ -151,10 +151,8 @@ __global__ __launch_bounds__(kBlock, CNSN_BNHEAD_WG_PER_CU) void nhwc_bnhead_fwd
 #pragma unroll
         for (int j = 0; j < VEC; ++j) Kc[j] = Kb[j] = acc[0][j] = acc[1][j] = acc[2][j] = acc2[0][j] = acc2[1][j] = 0.f;
         if (t.active) {
-            const size_t o = t.elem(g, 0);
-            const Vec<T, VEC> c0 = load_vec<T, VEC>(cv + o), b0 = load_vec<T, VEC>(idt + o);
-#pragma unroll
-            for (int j = 0; j < VEC; ++j) Kc[j] = to_float(c0.v[j]), Kb[j] = to_float(b0.v[j]);
+            nhwc_shift<T, VEC, false>(g, t, cv, nullptr, Kc);
+            nhwc_shift<T, VEC, false>(g, t, idt, nullptr, Kb);
             auto eat = [&](const Vec<T, VEC>& vc, const Vec<T, VEC>& vb) {
 #pragma unroll
                 for (int j = 0; j < VEC; ++j) {

@@ -46,6 +46,7 @@ NhwcGeom nhwc_fused_geom(const Plan& pl) {
     g.mchunk = (g.M + S - 1) / S;
     g.S = (g.M + g.mchunk - 1) / g.mchunk;
     g.P = pl.P;
+    nhwc_shift_samples(g, p.H, p.W);
     return g;
 }
 

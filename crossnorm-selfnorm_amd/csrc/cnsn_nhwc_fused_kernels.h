@@ -8,7 +8,7 @@
 // the NCHW cluster kernels (profiles/r05_nhwc.md).  Here the three phases are ONE grid of co-resident workgroups separated by
 // two grid-wide barriers:
 //   A  every workgroup walks its tiles (instance, pixel chunk, column block): column sums of X = x [+ addend] about the plane's
-//      first pixel; rows merged in LDS, written as partial moments  [chunk][2][plane]
+//      shift (nhwc_shift); rows merged in LDS, written as partial moments  [chunk][2][plane]
 //   -- barrier --
 //   B  the per-plane algebra, a workgroup per GC adjacent channels, a thread per instance: partial moments -> mean, std ->
 //      z = w0*mean + w1*std -> BatchNorm1d over the batch (block sums in double) -> gate g; writes the apply coefficient
@@ -79,7 +79,7 @@ struct NhwcFusedArgs {
     float eps_sn, eps_bn, momentum;
     double inv_n, unbias_n;
     float* part;    // [S][2][P] partial sums of the tiles
-    float* kshift;  // [P] forward: the shift the sums are taken about (X at the plane's first pixel)
+    float* kshift;  // [P] forward: the shift the sums are taken about (nhwc_shift: the median of X at three pixels of the plane)
     float* gout;    // [P] forward: the gate as the apply phase reads it (the SL_G row of `slim` when there is one)
     float* coefb;   // [2][P] backward: cX, c0
     float* slim;    // forward: written (may be null); backward: read
@@ -199,8 +199,8 @@ __device__ __forceinline__ void store_group(float* __restrict__ p, const float (
 // forward
 // ================================================================================================
 // Phase A of the forward (every single-launch forward runs it): each workgroup walks its tiles (instance, pixel chunk, column
-// block) and writes the column sums of X = x [+ addend] about the plane's first pixel as partial moments [chunk][2][plane]
-// (a.part, write-through) and that shift (a.kshift); SUM: X is also written to xsum
+// block) and writes the column sums of X = x [+ addend] about the plane's shift (nhwc_shift) as partial moments
+// [chunk][2][plane] (a.part, write-through) and that shift (a.kshift); SUM: X is also written to xsum
 template <typename T, int VEC, int ADD, bool KEEP, bool SUM>
 __device__ __forceinline__ void nhwc_fwd_phase_a(const NhwcFusedArgs& a, const T* __restrict__ x, const T* __restrict__ addend, T* xsum,
                                                  float* lds) {
@@ -211,12 +211,7 @@ __device__ __forceinline__ void nhwc_fwd_phase_a(const NhwcFusedArgs& a, const T
 #pragma unroll
         for (int j = 0; j < VEC; ++j) K[j] = acc[0][j] = acc[1][j] = 0.f;
         if (t.active) {
-            const size_t o = t.elem(g, 0);
-            const Vec<T, VEC> v0 = load_vec<T, VEC>(x + o);
-            Vec<T, VEC> b0 = v0;
-            if constexpr (ADD == ADD_PRE) b0 = load_vec<T, VEC>(addend + o);
-#pragma unroll
-            for (int j = 0; j < VEC; ++j) K[j] = ADD == ADD_PRE ? sum_t<T>(to_float(v0.v[j]), to_float(b0.v[j])) : to_float(v0.v[j]);
+            nhwc_shift<T, VEC, ADD == ADD_PRE>(g, t, x, addend, K);
             constexpr int U = ADD == ADD_PRE ? 2 : 4;
             auto eat = [&](const Vec<T, VEC>& va, const Vec<T, VEC>& vb, size_t e) {
                 Vec<T, VEC> keep;

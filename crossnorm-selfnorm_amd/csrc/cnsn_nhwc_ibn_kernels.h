@@ -4,7 +4,7 @@
 // every channel, :65,:117-121,:138-139), each followed by the block's ReLU.
 //
 // Same structure as the SelfNorm kernels of cnsn_nhwc_fused_kernels.h (tiles, grid barrier, write-through side arrays, give-up):
-//   A  column sums of X per plane about the plane's first pixel (nhwc_fwd_phase_a, unchanged)
+//   A  column sums of X per plane about the plane's shift (nhwc_fwd_phase_a, unchanged)
 //   -- barrier --
 //   B  a workgroup per GC adjacent channels (all InstanceNorm or all BatchNorm: half % GC == 0), a thread per instance:
 //        IN  per plane: mean, BIASED variance over H*W -> r = 1/sqrt(var + eps_in), a = w*r

@@ -11,8 +11,9 @@
 // A workgroup takes one instance n, one chunk of its pixels and up to 256 vector columns (a vector = 16 bytes = VEC adjacent
 // channels of one pixel): thread (r, col) walks the pixels p0 + r, p0 + r + rows, ... of its column with full-width loads and
 // keeps VEC accumulator pairs; the rows of a block are added in LDS in a fixed order, the pixel chunks of an instance by a
-// finishing kernel in a fixed order: no atomics, results are reproducible.  Sums are taken about the plane's first pixel
-// (the shift K of cnsn_stream_kernels.h), so S2 - S1^2/M does not cancel for planes with |mean| >> std.
+// finishing kernel in a fixed order: no atomics, results are reproducible.  Sums are taken about the median of three pixels
+// inside the plane (the shift of cnsn_device.h: NhwcGeom::ks, nhwc_shift), so S2 - S1^2/M does not cancel for planes with
+// |mean| >> std and an atypical border pixel costs nothing.
 // Un-boxed calls only (crop boxes would need the pixel's row / column per element): the host declines the others.
 #pragma once
 #include "cnsn_fused_stream_kernels.h"
@@ -31,8 +32,13 @@ struct NhwcGeom {
     int ncb;     // column blocks: ceil(tc / tcb)
     int S;       // pixel chunks per instance
     int mchunk;  // pixels per chunk (the last one may be shorter)
+    int ks[3];   // the pixels the shift of the one-pass sums is the median of (shift_sample_pixel, cnsn_device.h)
     size_t P;    // planes: N * C
 };
+
+inline void nhwc_shift_samples(NhwcGeom& g, int H, int W) {
+    for (int i = 0; i < 3; ++i) g.ks[i] = shift_sample_pixel(H, W, i);
+}
 
 template <int VEC>
 struct NhwcThread {
@@ -108,6 +114,25 @@ struct CohBuf {
     }
 };
 
+// The shift of an active thread's sums: per channel of its vector the median of X = x [+ addend] at the plane's three sample
+// pixels.  Every thread of every tile of a plane computes the same K, so the chunks' sums merge by plain addition.
+template <typename T, int VEC, bool ADD>
+__device__ __forceinline__ void nhwc_shift(const NhwcGeom& g, const NhwcThread<VEC>& t, const T* __restrict__ x,
+                                           const T* __restrict__ addend, float (&K)[VEC]) {
+    float s[3][VEC];
+#pragma unroll
+    for (int i = 0; i < 3; ++i) {
+        const size_t o = t.elem(g, g.ks[i]);
+        const Vec<T, VEC> v = load_vec<T, VEC>(x + o);
+        Vec<T, VEC> b = v;
+        if constexpr (ADD) b = load_vec<T, VEC>(addend + o);
+#pragma unroll
+        for (int j = 0; j < VEC; ++j) s[i][j] = ADD ? sum_t<T>(to_float(v.v[j]), to_float(b.v[j])) : to_float(v.v[j]);
+    }
+#pragma unroll
+    for (int j = 0; j < VEC; ++j) K[j] = median3(s[0][j], s[1][j], s[2][j]);
+}
+
 // rows of a block -> one value per (column, channel-in-vector, accumulator), fixed order; lds: [NACC][rows][tcb*VEC] floats
 // (COH: the partial sums are read by other workgroups of the same launch)
 template <int VEC, int NACC, bool COH = false>
@@ -154,7 +179,7 @@ __device__ __forceinline__ void nhwc_rows_sum(const NhwcGeom& g, const NhwcThrea
 }
 
 // ------------------------------------------------------------------------------------------------
-// pass A: per-(n, c) sums of (X - K), (X - K)^2 over a pixel chunk; X = x [+ addend] (ADD_PRE), K = X at pixel 0
+// pass A: per-(n, c) sums of (X - K), (X - K)^2 over a pixel chunk; X = x [+ addend] (ADD_PRE), K = nhwc_shift
 // ------------------------------------------------------------------------------------------------
 template <typename T, int VEC, int ADD>
 __global__ __launch_bounds__(kBlock) void nhwc_stats_kernel(const T* __restrict__ x, const T* __restrict__ addend, NhwcGeom g,
@@ -166,12 +191,7 @@ __global__ __launch_bounds__(kBlock) void nhwc_stats_kernel(const T* __restrict_
 #pragma unroll
     for (int j = 0; j < VEC; ++j) K[j] = acc[0][j] = acc[1][j] = 0.f;
     if (t.active) {
-        const size_t o = t.elem(g, 0);
-        const Vec<T, VEC> v0 = load_vec<T, VEC>(x + o);
-        Vec<T, VEC> b0 = v0;
-        if constexpr (ADD == ADD_PRE) b0 = load_vec<T, VEC>(addend + o);
-#pragma unroll
-        for (int j = 0; j < VEC; ++j) K[j] = ADD == ADD_PRE ? sum_t<T>(to_float(v0.v[j]), to_float(b0.v[j])) : to_float(v0.v[j]);
+        nhwc_shift<T, VEC, ADD == ADD_PRE>(g, t, x, addend, K);
         constexpr int U = ADD == ADD_PRE ? 2 : 4;
         int p = t.p0 + t.r;
         for (; p + (U - 1) * g.rows < t.p1; p += U * g.rows) {

@@ -69,7 +69,8 @@ __device__ __forceinline__ void lds_to_run(T* __restrict__ dst, long long byte0,
 // the driver.  Op provides:
 //   static constexpr int NIN, NOUT, NSC;   staged input tensors, output tensors (out t reuses in t's LDS), scalars
 //   void fetch(int p, float* sc) const;            per-plane scalars of plane p -> sc[0..NSC) (global loads)
-//   Acc  begin(const float* sc, const float* first) const;   first[t] = element 0 of the plane in tensor t
+//   Acc  begin(const float* sc, const float* samp) const;    samp[i * NIN + t] = the plane's sample pixel i (shift_sample_pixel,
+//                                                            cnsn_device.h) in tensor t
 //   void elem(Acc&, const float* sc, const float (&f)[NIN], bool ic, bool is, float (&o)[NOUT>0?NOUT:1]) const;
 //   void end(Acc&, const float* sc, int p, bool leader) const;      after the 16-lane reduction inside
 // ------------------------------------------------------------------------------------------------
@@ -105,10 +106,14 @@ __global__ __launch_bounds__(kBlock) void packed_kernel(PackedGeom g, const T* _
                 if (p >= g.P) break;  // uniform within the 16-lane group (and planes only grow with pl)
                 const float* sc = scal + pl * NSC;
                 const size_t eoff = (size_t)pl * g.M;
-                float first[NIN];
+                float samp[3 * NIN];
 #pragma unroll
-                for (int t = 0; t < NIN; ++t) first[t] = to_float(((const T*)(stage + (size_t)t * region))[eoff]);
-                auto acc = op.begin(sc, first);
+                for (int i = 0; i < 3; ++i) {
+                    const int e = shift_sample_pixel(g.M / g.Wd, g.Wd, i);
+#pragma unroll
+                    for (int t = 0; t < NIN; ++t) samp[i * NIN + t] = to_float(((const T*)(stage + (size_t)t * region))[eoff + e]);
+                }
+                auto acc = op.begin(sc, samp);
                 int r = 0, c = l16;  // (row, column) of this lane's element; only the boxed variants look at them
                 if constexpr (BOXED) {
                     r = l16 / g.Wd;
@@ -164,12 +169,19 @@ struct PackedStatsOp {
         else
             return f[0];
     }
-    __device__ __forceinline__ Acc begin(const float*, const float* first) const {
+    __device__ __forceinline__ Acc begin(const float*, const float* samp) const {
         Acc a;
-        float f[NIN];
+        float s[3];
 #pragma unroll
-        for (int t = 0; t < NIN; ++t) f[t] = first[t];
-        a.K = x_of(f);  // shift: sums are taken about the plane's first element (no cancellation for |mean| >> std)
+        for (int i = 0; i < 3; ++i) {
+            float f[NIN];
+#pragma unroll
+            for (int t = 0; t < NIN; ++t) f[t] = samp[i * NIN + t];
+            s[i] = x_of(f);
+        }
+        // shift: sums are taken about the median of the plane's three sample pixels (no cancellation for |mean| >> std, and no
+        // border pixel can make it atypical: cnsn_device.h)
+        a.K = median3(s[0], s[1], s[2]);
 #pragma unroll
         for (int k = 0; k < (BOXED ? 6 : 2); ++k) a.a[k] = 0.f;
         return a;

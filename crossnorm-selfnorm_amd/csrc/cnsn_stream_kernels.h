@@ -93,9 +93,20 @@ struct PlaneId {
 //   boxed   : out[0..5] = mean/M2 inside the content box, outside it, inside the style box
 //   fin != NULL: fin[0]=mean, fin[1]=sqrt(M2/(cnt-1)+eps) of the (content-box) region, float32
 //   moments are written as double: the mid kernels keep every per-plane scalar in double
-// Sums are taken about a per-plane shift K (mean of the plane's first VEC elements) so that
-// S2 - S1^2/cnt does not cancel for planes with |mean| >> std (post-ReLU activations).
+// Sums are taken about a per-plane shift K so that S2 - S1^2/cnt does not cancel for planes with
+// |mean| >> std (post-ReLU activations): the median of the means of the three vectors that hold the plane's
+// sample pixels (plane_shift; the shift of cnsn_device.h).
 // ------------------------------------------------------------------------------------------------
+// the shift of a plane's sums; load(e): the mean of the VEC elements from element e of the plane (e a multiple of VEC, and VEC
+// divides the plane: the vector lies inside it)
+template <int VEC, typename Load>
+__device__ __forceinline__ float plane_shift(const Geom& g, Load&& load) {
+    float s[3];
+#pragma unroll
+    for (int i = 0; i < 3; ++i) s[i] = load((size_t)(shift_sample_pixel(g.M / g.Wd, g.Wd, i) / VEC) * VEC);
+    return median3(s[0], s[1], s[2]);
+}
+
 template <typename T, int VEC, int LPP, bool BOXED>
 __global__ __launch_bounds__(kBlock) void plane_stats_kernel(const T* __restrict__ x, Geom g,
                                                              double* __restrict__ mom, float* __restrict__ fin,
@@ -105,13 +116,13 @@ __global__ __launch_bounds__(kBlock) void plane_stats_kernel(const T* __restrict
     const PlaneId<LPP> id(g.P);
     const T* base = x + (size_t)id.p * g.M;
 
-    float K = 0.f;
-    {
-        const Vec<T, VEC> f = load_vec<T, VEC>(base);
+    const float K = plane_shift<VEC>(g, [&](size_t e) {
+        const Vec<T, VEC> f = load_vec<T, VEC>(base + e);
+        float m = 0.f;
 #pragma unroll
-        for (int j = 0; j < VEC; ++j) K += to_float(f.v[j]);
-        K *= (1.0f / VEC);
-    }
+        for (int j = 0; j < VEC; ++j) m += to_float(f.v[j]);
+        return m * (1.0f / VEC);
+    });
     // one accumulator per vector slot: VEC short chains instead of one long one (rounding error of
     // a sequential fp32 sum grows with its length), folded pairwise afterwards
     float part[NACC][VEC];

@@ -187,8 +187,9 @@ def test_momentum_none_cumulative_average():
 @pytest.mark.parametrize("dtype", DTYPES, ids=IDS)
 @pytest.mark.parametrize("addend", [False, True], ids=["x", "x+a"])
 def test_constant_channel_and_mean_1000_sigma(dtype, addend):
-    """channel 0 constant (variance 0: rstd = 1/sqrt(eps)), channel 1 with mean = 1 000 sigma: the sums are taken about the
-    tensor's first row, so sum (x - k)^2 - (sum (x - k))^2 / R does not cancel.  Observed on the MI355X, fp32, y:
+    """channel 0 constant (variance 0: rstd = 1/sqrt(eps)), channel 1 with mean = 1 000 sigma: the sums are taken about a
+    shift k read from the tensor (the median of three of its rows), so sum (x - k)^2 - (sum (x - k))^2 / R does not cancel.
+    Observed on the MI355X with k = the first row, fp32, y:
     err 9.0e-06 against a bound of 6.3e-05 (twice the 2.1e-05 of torch's own fp32 BatchNorm2d against float64)."""
     m = run_case((32, 16, 12, 12), dtype, relu=True, addend=addend, special=True, seed=5)
     print(f"  margin of y: err {m['y'][0]:.3e} against {m['y'][1]:.3e}")

@@ -89,16 +89,20 @@ def compare(name, got, t64, t32, dtype, param=False):
         scale = max(1.0, float(t64.abs().max()))
         noise = float((t32 - t64).abs().max())
         err = float((got - t64).abs().max())
-        assert err <= max(1e-5 * scale, 2 * noise), f"{name}: err {err:.3e}, oracle32 noise {noise:.3e}, scale {scale:.3g}"
+        bound = max(1e-5 * scale, 2 * noise)
+        print(f"    {name}: err {err:.3e} bound {bound:.3e} (oracle32 noise {noise:.3e}, scale {scale:.3g})")
+        assert err <= bound, f"{name}: err {err:.3e}, oracle32 noise {noise:.3e}, scale {scale:.3g}"
     else:
         err = float((got - t32).abs().max())
         ref = max(float(t32.abs().max()), 1e-6)
         bound = 1e-2 * ref if not param else 1e-2 * ref + 1e-5
+        print(f"    {name}: err {err:.3e} bound {bound:.3e}")
         assert err <= bound, f"{name}: err {err:.3e} vs max {ref:.3e}"
 
 
 def run_case(shape, dtype, half, relu=True, addend=False, training=True, affine=True, momentum=0.1, const_plane=False, seed=0,
-             expect_fused=True, ref_dev=torch.device("cpu")):
+             expect_fused=True, ref_dev=torch.device("cpu"), edit=None):
+    """edit(x64, a64): changes the drawn float64 inputs in place before anything reads them (test_gpu_shift_sample.py)"""
     n, c, h, w = shape
     gen = torch.Generator().manual_seed(seed)
     x64 = torch.randn(shape, generator=gen, dtype=torch.float64) * 1.5 + torch.randn(n, c, 1, 1, generator=gen, dtype=torch.float64)
@@ -109,6 +113,8 @@ def run_case(shape, dtype, half, relu=True, addend=False, training=True, affine=
         if a64 is not None:
             a64[0, 0] = 0.0
         gy64[0, 0] = 0.0        # (kept out of the parameter gradients, as test_gpu_ibn.py does)
+    if edit is not None:
+        edit(x64, a64)
     mod = make_module(c, half, affine, momentum, seed)
     mod.train(training)
     twin64 = make_module(c, half, affine, momentum, seed).train(training)     # (state before the call, for the references)
@@ -148,7 +154,9 @@ def run_case(shape, dtype, half, relu=True, addend=False, training=True, affine=
         for k in ("running_mean", "running_var"):
             t64 = r64[3][k].double().cpu()
             err = float((st[k].double().cpu() - t64).abs().max())
-            assert err <= (1e-5 if dtype == torch.float32 else 1e-2) * max(1.0, float(t64.abs().max())), f"{k}: err {err:.3e}"
+            bound = (1e-5 if dtype == torch.float32 else 1e-2) * max(1.0, float(t64.abs().max()))
+            print(f"    {k}: err {err:.3e} bound {bound:.3e}")
+            assert err <= bound, f"{k}: err {err:.3e}"
     return y
 
 

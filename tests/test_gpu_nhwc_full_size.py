@@ -109,13 +109,16 @@ def rnd(t, dtype):
     return t + (t.detach().to(dtype).to(t.dtype) - t.detach())
 
 
-def make_inputs(shape, dtype, seed, scale_b=0.7):
+def make_inputs(shape, dtype, seed, scale_b=0.7, edit=None):
+    """edit(x, b): changes the drawn inputs in place before they are rounded to `dtype` (test_gpu_shift_sample.py)"""
     g = torch.Generator(device=DEV).manual_seed(seed)
     n, c = shape[:2]
     x = torch.randn(shape, generator=g, device=DEV)
     x.mul_(torch.rand(n, c, 1, 1, generator=g, device=DEV) * 1.5 + 0.5).add_(torch.randn(n, c, 1, 1, generator=g, device=DEV))
     b = torch.randn(shape, generator=g, device=DEV).mul_(scale_b)
     gy = torch.randn(shape, generator=g, device=DEV)
+    if edit is not None:
+        edit(x, b)
     return x.to(dtype), b.to(dtype), gy.to(dtype)
 
 
@@ -149,6 +152,7 @@ class Checker:
         _record(dict(self.row, shape=list(self.shape), dtype=str(self.dtype).replace("torch.", "").replace("float32", "fp32"), out=name,
                      err=err, scale=scale, oracle32_noise=noise, bound=bound, rel_tol=rel, keep=keep, oracle32_on="gpu",
                      rounding_spread=spread))
+        print(f"    {name}: err {err:.3e} bound {bound:.3e} (oracle32 noise {noise:.3e}, scale {scale:.3g})")
         assert err <= bound, f"{self.row} {self.shape} {self.dtype} {name}: err {err:.3e} > bound {bound:.3e} (oracle32 noise {noise:.3e}, scale {scale:.3g})"
 
 
@@ -196,13 +200,14 @@ def _drop_cache():
     free()
 
 
-def run_block(shape, dtype, mode, relu, fused, capfd, monkeypatch):
+def run_block(shape, dtype, mode, relu, fused, capfd, monkeypatch, edit=None):
+    """edit(x, b): make_inputs' hook (the cached inputs and oracle results are the edit's own)"""
     seed = 1000 + shape[1] + shape[0] + (7 if mode == "pre" else 0)
-    key = (tuple(shape), str(dtype), mode, relu)
+    key = (tuple(shape), str(dtype), mode, relu, edit)
     if key not in _case_cache.get("key", ()):
         _case_cache.clear()
         free()
-        _case_cache.update(key=(key,), inputs=make_inputs(shape, dtype, seed))
+        _case_cache.update(key=(key,), inputs=make_inputs(shape, dtype, seed, edit=edit))
     x, b, gy = _case_cache["inputs"]
     n, c = shape[:2]
     with knobs(monkeypatch, CNSN_NHWC_FUSED=fused, CNSN_DEBUG="1"), healthy():
@@ -330,10 +335,11 @@ def bn_oracle(conv, idt, gy, dtype, two, mask, seed, unfused=False):
     return out
 
 
-def run_bn_block(shape, dtype, two, capfd, monkeypatch, expect_fused=True):
+def run_bn_block(shape, dtype, two, capfd, monkeypatch, expect_fused=True, edit=None):
+    """edit(conv, idt): make_inputs' hook"""
     seed = 2000 + shape[1] + shape[0] + (3 if two else 0)
     free()
-    conv, idt, gy = make_inputs(shape, dtype, seed, scale_b=0.5)
+    conv, idt, gy = make_inputs(shape, dtype, seed, scale_b=0.5, edit=edit)
     c = shape[1]
     path = "bn-block" if expect_fused else "unfused"
     with knobs(monkeypatch, CNSN_DEBUG="1"), healthy():

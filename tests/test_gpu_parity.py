@@ -218,14 +218,17 @@ SHAPES = [
 ]
 
 
-def oracle_pair(shape, crop, kind, dtype, seed, lam=None, chan=False, is_two=False, training=True):
+def oracle_pair(shape, crop, kind, dtype, seed, lam=None, chan=False, is_two=False, training=True, edit=None):
     """inputs, draws and the oracle's results (fp64 truth + fp32) of one case: independent of the kernel strategy under
-    test, so computed once per case (tests/_memo.py) and shared by the strategies that run it"""
+    test, so computed once per case (tests/_memo.py) and shared by the strategies that run it.  edit(x64): changes the drawn
+    float64 input in place before anything reads it (test_gpu_shift_sample.py)"""
     torch.manual_seed(seed)
     np.random.seed(seed)
     n, c = shape[:2]
     x64 = cond_input(shape, seed)
     gy64 = torch.randn(shape, dtype=torch.float64)
+    if edit is not None:
+        edit(x64)
     if dtype != torch.float32:                     # identical quantised inputs for both sides
         x64 = x64.to(dtype).double()
         gy64 = gy64.to(dtype).double()
@@ -247,11 +250,11 @@ def oracle_pair(shape, crop, kind, dtype, seed, lam=None, chan=False, is_two=Fal
     return out
 
 
-def run_pair(shape, crop, kind, dtype, seed, lam=None, chan=False, is_two=False, training=True):
+def run_pair(shape, crop, kind, dtype, seed, lam=None, chan=False, is_two=False, training=True, edit=None):
     """Run oracle (fp64 truth + fp32) and the HIP modules on identical inputs/draws."""
     from tests._memo import memo
-    key = ("pair", tuple(shape), crop, kind, str(dtype), seed, lam, chan, is_two, training)
-    ora = memo(key, lambda: oracle_pair(shape, crop, kind, dtype, seed, lam, chan, is_two, training))
+    key = ("pair", tuple(shape), crop, kind, str(dtype), seed, lam, chan, is_two, training, edit)
+    ora = memo(key, lambda: oracle_pair(shape, crop, kind, dtype, seed, lam, chan, is_two, training, edit))
     x64, gy64, d = ora["x64"], ora["gy64"], ora["d"]
     n, c = shape[:2]
     out = {"t64": ora["t64"], "o32": ora["o32"]}
@@ -291,9 +294,11 @@ def assert_parity(out, dtype, ctx):
         e = float((got - truth).abs().max())
         if dtype == torch.float32:
             e32 = float((ref32 - truth).abs().max())
+            print(f"    {name}: err {e:.3e} bound {max(tol * scale, 2 * e32):.3e} (oracle32 noise {e32:.3e}, scale {scale:.3g})")
             assert e <= max(tol * scale, 2 * e32), f"{ctx} {name}: err {e:.3e} (oracle32 err {e32:.3e}, scale {scale:.3g})"
         else:
             e = float((got - ref32).abs().max())
+            print(f"    {name}: err {e:.3e} bound {1e-2 * max(float(ref32.abs().max()), 1e-3):.3e}")
             assert e <= 1e-2 * max(float(ref32.abs().max()), 1e-3), f"{ctx} {name}: err {e:.3e} vs max {float(ref32.abs().max()):.3g}"
 
     one("y", hip["y"], t64["y"], o32["y"], 1e-5)
