@@ -7,6 +7,7 @@ SelfNorm sites per forward at batch B, pos='post' (SURVEY.md §3.2): (B,256,56,5
 import torch
 import torch.nn as nn
 
+from .. import functional as _F
 from . import _sites
 from ._sites import CrossNormSites, make_cnsn, residual_sum
 from .bn_act import bn_act
@@ -44,19 +45,28 @@ class _Bottleneck(nn.Module):
         h = self.bn1.forward_act(h) if self.ibn == "a" else bn_act(self.bn1, h)
         h = bn_act(self.bn2, self.conv2(h))
         h = self.conv3(h)
-        if self.ibn == "b":                            # resnet_ibn_cnsn.py:108-122: relu(IN(bn3(h) + identity))
-            skip = x if self.downsample is None else self.downsample(x)
-            h = self.bn3(h)
-            if self.pos == "residual":
-                h = self.cnsn(h)
-            elif self.pos == "identity":
-                skip = self.cnsn(skip)
-            return self.IN.forward_act(h, skip, relu=True)
         # :99-122.  pos='post': bn3 (and the downsample's BatchNorm2d), the add, the CNSN unit and the ReLU are ONE call when the
         # unit offers it (this library's `CNSN.forward_bn_block`: one launch per direction on channels-last tensors, the
-        # un-fused sequence otherwise)
-        fb = getattr(getattr(self, "cnsn", None), "forward_bn_block", None) if (_sites.FUSE_BLOCK and self.pos == "post") else None
-        if fb is not None and h.is_cuda:
+        # un-fused sequence otherwise).  pos='residual': bn3, the unit, the add behind it and the ReLU (add_mode 'post'; IBN-b:
+        # bn3 and the unit, add_mode 'none', in front of the InstanceNorm2d's own launch); the downsample's BatchNorm2d is a
+        # `bn_act` launch of its own there (CNSN_BN_BLOCK=0: nn.BatchNorm2d as it is, like bn3).
+        fb = None
+        if _sites.FUSE_BLOCK and self.pos in ("post", "residual") and h.is_cuda:
+            fb = getattr(getattr(self, "cnsn", None), "forward_bn_block", None)
+        if self.ibn == "b":                            # resnet_ibn_cnsn.py:108-122: relu(IN(bn3(h) + identity))
+            skip = x if self.downsample is None else self._skip(x, fb is not None and _F._BN_BLOCK)
+            if fb is not None:                         # (pos='residual': at 'post' an IBN-b block has no unit)
+                h = fb(h, self.bn3, None, relu=False, add_mode="none")
+            else:
+                h = self.bn3(h)
+                if self.pos == "residual":
+                    h = self.cnsn(h)
+                elif self.pos == "identity":
+                    skip = self.cnsn(skip)
+            return self.IN.forward_act(h, skip, relu=True)
+        if fb is not None and self.pos == "residual":
+            return fb(h, self.bn3, x if self.downsample is None else self._skip(x, _F._BN_BLOCK), relu=True, add_mode="post")
+        if fb is not None:
             if self.downsample is None:
                 return fb(h, self.bn3, x, relu=True)
             if len(self.downsample) == 2 and isinstance(self.downsample[1], nn.BatchNorm2d):
@@ -66,6 +76,13 @@ class _Bottleneck(nn.Module):
         if getattr(self, "cnsn", None) is None:        # no unit here: the plain end relu(bn3(h) + skip)
             return bn_act(self.bn3, h, skip)
         return residual_sum(self.cnsn, self.pos, self.bn3(h), skip, relu=True)
+
+    def _skip(self, x, own_launch):
+        """the downsample path; `own_launch`: a `Sequential(conv, BatchNorm2d)` runs its BatchNorm2d through `bn_act`"""
+        down = self.downsample
+        if own_launch and len(down) == 2 and isinstance(down[1], nn.BatchNorm2d):
+            return bn_act(down[1], down[0](x), relu=False)
+        return down(x)
 
 
 class ResNet50CNSN(nn.Module, CrossNormSites):

@@ -348,9 +348,15 @@ class CNSN(nn.Module):
         cfg = FusedConfig(add_mode=add_mode, relu=bool(relu), **kw)
         return _F.fused_cnsn(x, cfg, perm=perm, chan_perm=chan, g=g, f=f, addend=addend)
 
-    def forward_bn_block(self, conv_out, bn, identity, relu=True, identity_bn=None):
+    def forward_bn_block(self, conv_out, bn, identity, relu=True, identity_bn=None, add_mode="pre"):
         """`act(self(bn(conv_out) + identity))` — the tail of a ResNet bottleneck:
             out = self.bn3(out); out += identity; out = self.cnsn(out); out = self.relu(out)    (imagenet/resnet_cnsn.py:108-122)
+        add_mode 'post': `act(self(bn(conv_out)) + identity)`, the tail at pos='residual' (:112-122):
+            out = self.bn3(out); out = self.cnsn(out); out += identity; out = self.relu(out)
+        add_mode 'none': `self(bn(conv_out))`, `identity` None (allowed for this mode only) — what stands in front of the IBN-b
+        block's InstanceNorm2d at pos='residual' (imagenet/resnet_ibn_cnsn.py:109-127).  4 + 8 tensor passes ('post' with the
+        ReLU), 3 + 5 ('none') instead of BatchNorm2d's 3 + 5 and the op's 4 + 8 / 3 + 5.  With `identity_bn` these two modes run
+        the un-fused sequence.
         `identity_bn`: the skip path ends in a BatchNorm2d of its own (the block's `downsample`, :99-100) and `identity` is the
         INPUT of that layer — `act(self(bn(conv_out) + identity_bn(identity)))`.
         ONE launch per direction when the fused kernels take the call (`functional.bn_block_plan`: channels-last tensors,
@@ -358,24 +364,30 @@ class CNSN(nn.Module):
         mode, N <= 256): 13 tensor passes per block and step instead of BatchNorm2d's 8 (16 with the downsample's) + the op's 10;
         otherwise the same steps as separate calls (the BatchNorm2d layers, then `forward_block`).  BatchNorm2d's per-call
         book-keeping (`num_batches_tracked`, `momentum=None`) is done here exactly as `nn.BatchNorm2d.forward` does it."""
+        assert add_mode in ("pre", "post", "none")
+        assert (identity is None) == (add_mode == "none")
         cn, sn = self.crossnorm, self.selfnorm
         armed = cn is not None and cn.active
 
         def plain(m):
             return type(m) is nn.BatchNorm2d and m.affine and m.track_running_stats and m.training
-        fused = (plain(bn) and (identity_bn is None or plain(identity_bn)) and sn is not None
+        fused = (plain(bn) and (identity_bn is None or (add_mode == "pre" and plain(identity_bn))) and sn is not None
                  and type(sn) is SelfNorm and sn.f_fc is None and sn._fusable() and not armed and conv_out.is_cuda
-                 and (cn is None or type(cn) is CrossNorm) and identity.shape == conv_out.shape
-                 and identity.dtype == conv_out.dtype and not torch.cuda.is_current_stream_capturing())
+                 and (cn is None or type(cn) is CrossNorm)
+                 and (identity is None or (identity.shape == conv_out.shape and identity.dtype == conv_out.dtype))
+                 and not (add_mode == "none" and relu) and not torch.cuda.is_current_stream_capturing())
         if fused:
             kw, _, _ = sn._fused_args_peek()
-            fused = kw["sn_training"] and _F.bn_block_plan(conv_out, FusedConfig(add_mode="pre", relu=bool(relu), **kw))
+            fused = kw["sn_training"] and _F.bn_block_plan(conv_out, FusedConfig(add_mode=add_mode, relu=bool(relu), **kw))
         if not fused:
             skip = identity if identity_bn is None else identity_bn(identity)
-            return self.forward_block(bn(conv_out), skip, add_mode="pre", relu=relu)
+            if add_mode == "none":
+                y = self(bn(conv_out))
+                return torch.relu(y) if relu else y
+            return self.forward_block(bn(conv_out), skip, add_mode=add_mode, relu=relu)
         kw, g, _ = sn._fused_args()
         _, bn_eps, bn_mom, bn_counter = SelfNorm._bn_call_state(bn, in_kernel=True)
-        cfg = FusedConfig(add_mode="pre", relu=bool(relu), **kw)
+        cfg = FusedConfig(add_mode=add_mode, relu=bool(relu), **kw)
         extra = ()
         if identity_bn is not None:
             _, e2, m2, c2 = SelfNorm._bn_call_state(identity_bn, in_kernel=True)

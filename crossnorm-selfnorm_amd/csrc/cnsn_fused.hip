@@ -137,7 +137,9 @@ int bn_block_parse(const cnsn_problem_t* prob, const cnsn_epilogue_t* epi, const
     st = make_plan(prob, pl);
     if (st) return st;
     if (bn && bn->struct_bytes != (int32_t)sizeof(cnsn_bn_tail_t)) return CNSN_E_STRUCT;
-    if (pl.pr.layout != CNSN_LAYOUT_NHWC || e.add != ADD_PRE || e.sum_out || !nhwc_bnhead_ok(pl, check_health) || (bn && !bn->training))
+    // (every add mode; without an add there is no ReLU either: that call is the IBN-b block's, whose InstanceNorm2d has its own)
+    if (pl.pr.layout != CNSN_LAYOUT_NHWC || (e.add == ADD_NONE && e.relu) || e.sum_out || !nhwc_bnhead_ok(pl, check_health) ||
+        (bn && !bn->training))
         return CNSN_E_UNSUPPORTED;
     return CNSN_OK;
 }
@@ -161,10 +163,11 @@ int cnsn_forward_bn_block(const cnsn_problem_t* prob, const cnsn_epilogue_t* epi
     EpiPlan e;
     const int st = bn_block_parse(prob, epi, bn, pl, e, false);
     if (st) return st;
+    if (bn_skip && e.add != ADD_PRE) return CNSN_E_UNSUPPORTED;  // (a BatchNorm2d on the skip path: in front of the op only)
     if (!conv_out || !y || !workspace || !bn_stats || !bn->weight || !bn->bias || !bn->running_mean || !bn->running_var) return CNSN_E_NULL;
     if ((((uintptr_t)conv_out | (uintptr_t)y | (uintptr_t)workspace | (uintptr_t)bn_stats) & 15u) != 0) return CNSN_E_ALIGN;
     if (!gate_ok(g)) return CNSN_E_NULL;
-    return nhwc_bnhead_forward(pl, e.relu, *bn, bn_skip, conv_out, e.addend, gate_dev(g), y, saved, bn_stats, workspace, workspace_bytes,
+    return nhwc_bnhead_forward(pl, e.add, e.relu, *bn, bn_skip, conv_out, e.addend, gate_dev(g), y, saved, bn_stats, workspace, workspace_bytes,
                                (hipStream_t)stream_);
 }
 
@@ -180,12 +183,16 @@ int cnsn_backward_bn_block(const cnsn_problem_t* prob, const cnsn_epilogue_t* ep
     EpiPlan e;
     const int st = bn_block_parse(prob, epi, bn, pl, e, false, false);
     if (st) return st;
-    if (!grad_y || !conv_out || !grad_conv_out || !grad_identity || !saved || !bn_stats || !workspace || !bn->weight) return CNSN_E_NULL;
+    if (bn_skip && e.add != ADD_PRE) return CNSN_E_UNSUPPORTED;
+    // (grad_identity: written with a PRE add and with a POST add behind a ReLU; otherwise it is grad_y itself, or there is no identity)
+    const bool writes_identity = e.add == ADD_PRE || (e.add == ADD_POST && e.relu);
+    if (!grad_y || !conv_out || !grad_conv_out || (writes_identity && !grad_identity) || !saved || !bn_stats || !workspace || !bn->weight)
+        return CNSN_E_NULL;
     if ((((uintptr_t)grad_y | (uintptr_t)conv_out | (uintptr_t)grad_conv_out | (uintptr_t)grad_identity | (uintptr_t)workspace |
           (uintptr_t)bn_stats) & 15u) != 0)
         return CNSN_E_ALIGN;
     if (!gate_ok(g) || !dg || !dg->d_fc_weight || !dg->d_bn_weight || !dg->d_bn_bias) return CNSN_E_NULL;
-    return nhwc_bnhead_backward(pl, e.relu, *bn, bn_skip, grad_y, conv_out, e.addend, gate_dev(g), saved, bn_stats, grad_conv_out,
+    return nhwc_bnhead_backward(pl, e.add, e.relu, *bn, bn_skip, grad_y, conv_out, e.addend, gate_dev(g), saved, bn_stats, grad_conv_out,
                                 grad_identity, gate_grad_dev(dg), d_bn_weight, d_bn_bias, d_bn_skip_weight, d_bn_skip_bias, workspace,
                                 workspace_bytes, (hipStream_t)stream_);
 }

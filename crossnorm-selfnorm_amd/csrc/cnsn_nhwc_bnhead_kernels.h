@@ -30,6 +30,11 @@
 // per channel, so the same five plane sums give both BatchNorm2d's batch statistics and the statistics of X; the backward writes
 // the gradients of the two convolution outputs where it wrote those of conv_out and the identity.  Same 13 passes; the
 // downsample's BatchNorm2d costs nothing any more.
+//
+// ADD (round 9): the identity BEHIND the op, or none — the tail at pos='residual' (resnet_cnsn.py:112-122; the IBN-b blocks of
+// resnet_ibn_cnsn.py:109-127): y = act(g * T(alpha*c + beta) + identity) (ADD_POST), y = g * T(alpha*c + beta) (ADD_NONE).
+// Phase A reads conv_out alone, phase C (C') reads the identity for the add (the mask); 4 + 8 passes (POST with the ReLU),
+// 3 + 5 (NONE); same workspace region, `saved` record and bn_stats as the PRE launch.  Not with TWO.
 #pragma once
 #include "cnsn_nhwc_fused_kernels.h"
 
@@ -111,18 +116,23 @@ __device__ __forceinline__ double pick(const double (&v)[GC], int j) {
     return r;
 }
 
+// x = T(alpha*c + beta): a BatchNorm2d's output, rounded where the layer stores it
+template <typename T>
+__device__ __forceinline__ float bn_out(float c, float alpha, float beta) {
+    return to_float(from_float<T>(fmaf(alpha, c, beta)));
+}
+
 // X = T(T(alpha*c + beta) + b): bn3's output and the in-place add, rounded where the un-fused sequence rounds them
 template <typename T>
 __device__ __forceinline__ float bn_sum(float c, float b, float alpha, float beta) {
-    const float x = to_float(from_float<T>(fmaf(alpha, c, beta)));
-    return sum_t<T>(x, b);
+    return sum_t<T>(bn_out<T>(c, alpha, beta), b);
 }
 
 // the skip path's value: the identity as it is, or (TWO) T(alpha2*c2 + beta2), the downsample BatchNorm2d's output
 template <typename T, bool TWO>
 __device__ __forceinline__ float bn_skip(float c2, float alpha2, float beta2) {
     if constexpr (TWO)
-        return to_float(from_float<T>(fmaf(alpha2, c2, beta2)));
+        return bn_out<T>(c2, alpha2, beta2);
     else
         return c2;
 }
@@ -134,18 +144,26 @@ constexpr int kBnBwd = 4;  // ... of the backward: sum G', G'*(X - mu), G'*(c - 
 // ================================================================================================
 // forward
 // ================================================================================================
-template <typename T, int VEC, bool KEEP, bool TWO>
+// ADD: where the identity enters.  ADD_PRE: in front of the op, as above.  ADD_POST / ADD_NONE (pos='residual'):
+//     y = act(g * T(alpha*c + beta) + identity)        /        y = g * T(alpha*c + beta)
+// the op's input is bn3's output alone, so phase A reads conv_out only (two sums per plane, the SelfNorm kernels' own phase A),
+// phase B runs with the identity's moments absent, and phase C adds the identity behind the gate: one rounding of g*x + identity,
+// where nhwc_fused_fwd_kernel<.., ADD_POST> rounds it.
+template <typename T, int VEC, bool KEEP, bool TWO, int ADD = ADD_PRE>
 __global__ __launch_bounds__(kBlock, CNSN_BNHEAD_WG_PER_CU) void nhwc_bnhead_fwd_kernel(NhwcBnArgs a, const T* __restrict__ cv,
                                                                                          const T* __restrict__ idt, T* __restrict__ y,
                                                                                          GateDev gg) {
+    static_assert(!TWO || ADD == ADD_PRE, "a BatchNorm2d on the skip path: the PRE add only");
     extern __shared__ float lds[];
     __shared__ double red[4 * kBnGc];
     __shared__ int bar_flag;
     constexpr int GC = kBnGc;
+    constexpr int NF = ADD == ADD_PRE ? kBnFwd : 2;  // part rows per pixel chunk
     const NhwcGeom& g = a.f.g;
 
-    // ---- A: five partial sums of every tile
-    for (int tile = blockIdx.x; tile < a.f.ntiles; tile += gridDim.x) {
+    // ---- A: five partial sums of every tile (two without a PRE add: [chunk][2][plane], the shift in a.f.kshift)
+    if constexpr (ADD != ADD_PRE) nhwc_fwd_phase_a<T, VEC, ADD_NONE, KEEP, false>(a.f, cv, nullptr, nullptr, lds);
+    for (int tile = blockIdx.x; ADD == ADD_PRE && tile < a.f.ntiles; tile += gridDim.x) {
         const NhwcThread<VEC> t(g, tile);
         float Kc[VEC], Kb[VEC], acc[3][VEC], acc2[2][VEC];
 #pragma unroll
@@ -206,15 +224,22 @@ __global__ __launch_bounds__(kBlock, CNSN_BNHEAD_WG_PER_CU) void nhwc_bnhead_fwd
         for (int j = 0; j < GC; ++j) Sc[j] = Qc[j] = Sb[j] = Qb[j] = Pcb[j] = 0.0;
         const CohBuf pb(a.f.part);
         for (int s = 0; s < g.S; ++s) {
-            const size_t base = (size_t)s * kBnFwd * g.P + p0;
+            const size_t base = (size_t)s * NF * g.P + p0;
             add_group_coh<GC>(pb, base, Sc);
             add_group_coh<GC>(pb, base + g.P, Qc);
-            add_group_coh<GC>(pb, base + 2 * g.P, Sb);
-            add_group_coh<GC>(pb, base + 3 * g.P, Qb);
-            add_group_coh<GC>(pb, base + 4 * g.P, Pcb);
+            if constexpr (ADD == ADD_PRE) {
+                add_group_coh<GC>(pb, base + 2 * g.P, Sb);
+                add_group_coh<GC>(pb, base + 3 * g.P, Qb);
+                add_group_coh<GC>(pb, base + 4 * g.P, Pcb);
+            }
         }
         load_group_coh<GC>(CohBuf(a.f.kshift), p0, Kc);
-        load_group_coh<GC>(CohBuf(a.kshift_b), p0, Kb);
+        if constexpr (ADD == ADD_PRE) {
+            load_group_coh<GC>(CohBuf(a.kshift_b), p0, Kb);
+        } else {  // (no identity in front of the op: its moments stay zero, and X = alpha*c + beta below)
+#pragma unroll
+            for (int j = 0; j < GC; ++j) Kb[j] = 0.0;
+        }
         const double M = (double)g.M;
         double mc[GC], M2c[GC], mb[GC], M2b[GC], Ccb[GC], t1[GC], m2d[GC], v2d[GC];
 #pragma unroll
@@ -386,13 +411,20 @@ __global__ __launch_bounds__(kBlock, CNSN_BNHEAD_WG_PER_CU) void nhwc_bnhead_fwd
             Vec<T, VEC> o;
 #pragma unroll
             for (int j = 0; j < VEC; ++j) {
-                const float b = bn_skip<T, TWO>(to_float(vb.v[j]), al2[TWO ? j : 0], be2[TWO ? j : 0]);
-                const float X = bn_sum<T>(to_float(vc.v[j]), b, al[j], be[j]);
-                const float v = gate[j] * X;  // one rounding, like the reference's x * g (:150)
+                float v;
+                if constexpr (ADD == ADD_PRE) {
+                    const float b = bn_skip<T, TWO>(to_float(vb.v[j]), al2[TWO ? j : 0], be2[TWO ? j : 0]);
+                    const float X = bn_sum<T>(to_float(vc.v[j]), b, al[j], be[j]);
+                    v = gate[j] * X;  // one rounding, like the reference's x * g (:150)
+                } else {
+                    v = gate[j] * bn_out<T>(to_float(vc.v[j]), al[j], be[j]);
+                    if constexpr (ADD == ADD_POST) v += to_float(vb.v[j]);  // (the expression of nhwc_fused_fwd_kernel<.., ADD_POST>)
+                }
                 o.v[j] = from_float<T>(relu ? fmaxf(v, 0.f) : v);
             }
             store_vec_nt<T, VEC>(y + e, o);
         };
+        constexpr bool RD_B = ADD != ADD_NONE;  // a second tensor to read
         constexpr int U = 2;
         const int cnt = (t.p1 - t.p0 - t.r + g.rows - 1) / g.rows;  // pixels of this thread in the chunk
         int q = cnt - 1;
@@ -402,14 +434,15 @@ __global__ __launch_bounds__(kBlock, CNSN_BNHEAD_WG_PER_CU) void nhwc_bnhead_fwd
             for (int u = 0; u < U; ++u) {
                 const size_t e = t.elem(g, t.p0 + t.r + (q - u) * g.rows);
                 vc[u] = load_vec_nt<T, VEC>(cv + e);
-                vb[u] = load_vec_nt<T, VEC>(idt + e);
+                if constexpr (RD_B) vb[u] = load_vec_nt<T, VEC>(idt + e);
             }
 #pragma unroll
-            for (int u = 0; u < U; ++u) emit(vc[u], vb[u], t.elem(g, t.p0 + t.r + (q - u) * g.rows));
+            for (int u = 0; u < U; ++u) emit(vc[u], RD_B ? vb[u] : vc[u], t.elem(g, t.p0 + t.r + (q - u) * g.rows));
         }
         for (; q >= 0; --q) {
             const size_t e = t.elem(g, t.p0 + t.r + q * g.rows);
-            emit(load_vec_nt<T, VEC>(cv + e), load_vec_nt<T, VEC>(idt + e), e);
+            const Vec<T, VEC> vc = load_vec_nt<T, VEC>(cv + e);
+            emit(vc, RD_B ? load_vec_nt<T, VEC>(idt + e) : vc, e);
         }
     }
 }
@@ -417,11 +450,16 @@ __global__ __launch_bounds__(kBlock, CNSN_BNHEAD_WG_PER_CU) void nhwc_bnhead_fwd
 // ================================================================================================
 // backward
 // ================================================================================================
-template <typename T, int VEC, bool KEEP, bool TWO>
+// ADD_POST (with the ReLU: its mask is that of g*x + identity, nhwc_pair<T, ADD_POST>) / ADD_NONE: X = T(alpha*c + beta) is the
+// op's input; the identity is read for the mask alone and its gradient is the masked G' (ADD_POST), or it is not there at all
+// (ADD_NONE: `idt`, `didt` are not touched).  A POST add without a ReLU runs as ADD_NONE: the identity's gradient is grad_y itself.
+template <typename T, int VEC, bool KEEP, bool TWO, int ADD = ADD_PRE>
 __global__ __launch_bounds__(kBlock, TWO ? 2 : CNSN_BNHEAD_WG_PER_CU) void nhwc_bnhead_bwd_kernel(NhwcBnArgs a, const T* __restrict__ gy,
                                                                                          const T* __restrict__ cv,
                                                                                          const T* __restrict__ idt, T* __restrict__ dconv,
                                                                                          T* __restrict__ didt, GateDev gg, GateGradDev dg) {
+    static_assert(!TWO || ADD == ADD_PRE, "a BatchNorm2d on the skip path: the PRE add only");
+    constexpr bool RD_B = ADD != ADD_NONE;  // the identity is read (and its gradient written)
     extern __shared__ float lds[];
     __shared__ double red[4 * 2 * kBnGc];
     __shared__ int bar_flag;
@@ -460,9 +498,14 @@ __global__ __launch_bounds__(kBlock, TWO ? 2 : CNSN_BNHEAD_WG_PER_CU) void nhwc_
 #pragma unroll
                 for (int j = 0; j < VEC; ++j) {
                     const float c = to_float(vc.v[j]), c2 = to_float(vb.v[j]);
-                    const float X = bn_sum<T>(c, bn_skip<T, TWO>(c2, al2[TWO ? j : 0], be2[TWO ? j : 0]), al[j], be[j]);
-                    float G = to_float(vg.v[j]);
-                    if (relu) G = relu_open<T>(gate[j] * X) ? G : 0.f;
+                    float G, X;
+                    if constexpr (ADD == ADD_PRE) {
+                        X = bn_sum<T>(c, bn_skip<T, TWO>(c2, al2[TWO ? j : 0], be2[TWO ? j : 0]), al[j], be[j]);
+                        G = to_float(vg.v[j]);
+                        if (relu) G = relu_open<T>(gate[j] * X) ? G : 0.f;
+                    } else {
+                        nhwc_pair<T, ADD>(to_float(vg.v[j]), bn_out<T>(c, al[j], be[j]), c2, gate[j], 0.f, 0.f, relu, G, X);
+                    }
                     acc[0][j] += G;
                     acc[1][j] = fmaf(G, X - mu[j], acc[1][j]);
                     acc[2][j] = fmaf(G, c - mch[j], acc[2][j]);
@@ -477,14 +520,15 @@ __global__ __launch_bounds__(kBlock, TWO ? 2 : CNSN_BNHEAD_WG_PER_CU) void nhwc_
                     const size_t e = t.elem(g, p + u * g.rows);
                     vg[u] = nhwc_ld<T, VEC, !KEEP>(gy + e);
                     vc[u] = nhwc_ld<T, VEC, !KEEP>(cv + e);
-                    vb[u] = nhwc_ld<T, VEC, !KEEP>(idt + e);
+                    if constexpr (RD_B) vb[u] = nhwc_ld<T, VEC, !KEEP>(idt + e);
                 }
 #pragma unroll
-                for (int u = 0; u < 2; ++u) eat(vg[u], vc[u], vb[u]);
+                for (int u = 0; u < 2; ++u) eat(vg[u], vc[u], RD_B ? vb[u] : vc[u]);
             }
             for (; p < t.p1; p += g.rows) {
                 const size_t e = t.elem(g, p);
-                eat(nhwc_ld<T, VEC, !KEEP>(gy + e), nhwc_ld<T, VEC, !KEEP>(cv + e), nhwc_ld<T, VEC, !KEEP>(idt + e));
+                const Vec<T, VEC> vc = nhwc_ld<T, VEC, !KEEP>(cv + e);
+                eat(nhwc_ld<T, VEC, !KEEP>(gy + e), vc, RD_B ? nhwc_ld<T, VEC, !KEEP>(idt + e) : vc);
             }
         }
         nhwc_rows_sum_part<VEC, 3, kBnBwd>(g, t, acc, 0, lds, a.f.part);
@@ -492,6 +536,7 @@ __global__ __launch_bounds__(kBlock, TWO ? 2 : CNSN_BNHEAD_WG_PER_CU) void nhwc_
     }
     if (!grid_barrier(a.f.bar, 1, &bar_flag)) {
         nhwc_mark_owed<T, VEC>(g, a.f.ntiles, dconv);
+        if constexpr (ADD == ADD_POST) nhwc_mark_owed<T, VEC>(g, a.f.ntiles, didt);  // (every output of the launch)
         return;
     }
 
@@ -627,6 +672,7 @@ __global__ __launch_bounds__(kBlock, TWO ? 2 : CNSN_BNHEAD_WG_PER_CU) void nhwc_
     }
     if (!grid_barrier(a.f.bar, 2, &bar_flag)) {
         nhwc_mark_owed<T, VEC>(g, a.f.ntiles, dconv);
+        if constexpr (ADD == ADD_POST) nhwc_mark_owed<T, VEC>(g, a.f.ntiles, didt);
         return;
     }
 
@@ -661,23 +707,29 @@ __global__ __launch_bounds__(kBlock, TWO ? 2 : CNSN_BNHEAD_WG_PER_CU) void nhwc_
 #pragma unroll
             for (int j = 0; j < VEC; ++j) {
                 const float c = to_float(vc.v[j]), c2 = to_float(vb.v[j]);
-                const float X = bn_sum<T>(c, bn_skip<T, TWO>(c2, al2[TWO ? j : 0], be2[TWO ? j : 0]), al[j], be[j]);
-                float G = to_float(vg.v[j]);
-                if (relu) G = relu_open<T>(cG[j] * X) ? G : 0.f;
+                float G, X;
+                if constexpr (ADD == ADD_PRE) {
+                    X = bn_sum<T>(c, bn_skip<T, TWO>(c2, al2[TWO ? j : 0], be2[TWO ? j : 0]), al[j], be[j]);
+                    G = to_float(vg.v[j]);
+                    if (relu) G = relu_open<T>(cG[j] * X) ? G : 0.f;
+                } else {
+                    nhwc_pair<T, ADD>(to_float(vg.v[j]), bn_out<T>(c, al[j], be[j]), c2, cG[j], 0.f, 0.f, relu, G, X);
+                }
                 const float dX = fmaf(cG[j], G, fmaf(cX[j], X - xr[j], c0[j]));
                 if constexpr (TWO)  // the gradient of the skip path's convolution output, through ITS BatchNorm2d
                     od.v[j] = from_float<T>(fmaf(al2[j], dX, fmaf(e1b[j], c2 - m2ch[j], e0b[j])));
                 else
-                    od.v[j] = from_float<T>(dX);
+                    od.v[j] = from_float<T>(ADD == ADD_PRE ? dX : G);  // (POST: the identity sits behind the gate, its gradient is the masked G')
                 o.v[j] = from_float<T>(fmaf(al[j], dX, fmaf(e1[j], c - mch[j], e0[j])));
             }
             store_vec_nt<T, VEC>(dconv + e, o);
-            store_vec_nt<T, VEC>(didt + e, od);
+            if constexpr (RD_B) store_vec_nt<T, VEC>(didt + e, od);
         };
         const int cnt = (t.p1 - t.p0 - t.r + g.rows - 1) / g.rows;
         for (int q = cnt - 1; q >= 0; --q) {
             const size_t e = t.elem(g, t.p0 + t.r + q * g.rows);
-            emit(load_vec_nt<T, VEC>(gy + e), load_vec_nt<T, VEC>(cv + e), load_vec_nt<T, VEC>(idt + e), e);
+            const Vec<T, VEC> vc = load_vec_nt<T, VEC>(cv + e);
+            emit(load_vec_nt<T, VEC>(gy + e), vc, RD_B ? load_vec_nt<T, VEC>(idt + e) : vc, e);
         }
     }
 }

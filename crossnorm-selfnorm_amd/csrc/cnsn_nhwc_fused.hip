@@ -155,6 +155,7 @@ void nhwc_saved_from_slim(const Plan& pl, const float* slim, int relu, double* s
 
 // ------------------------------------------------------------------------------------------------------------------------
 // the block's last BatchNorm2d in front of the op (cnsn_nhwc_bnhead_kernels.h): y = act(SelfNorm(BatchNorm2d(conv_out) + identity))
+// (ADD_PRE), y = act(SelfNorm(BatchNorm2d(conv_out)) + identity) (ADD_POST), y = SelfNorm(BatchNorm2d(conv_out)) (ADD_NONE)
 // ------------------------------------------------------------------------------------------------------------------------
 // check_health false: the BACKWARD of a forward that ran these kernels — there is no other kernel that reads its record, so it
 // runs them whatever has happened to the cluster strategy in between (a bounded wait at worst: DESIGN.md section 6)
@@ -183,20 +184,25 @@ NhwcBnArgs make_bn_args(const Plan& pl, const NhwcGeom& ng, int relu, const cnsn
     a.chan = w.chan;
     return a;
 }
+const char* add_name(int add) { return add == ADD_PRE ? "pre" : (add == ADD_POST ? "post" : "none"); }
+// the modes without a PRE add take no BatchNorm2d on the skip path, and ADD_NONE no ReLU (the IBN layer behind it has its own)
+bool bnhead_mode_ok(int add, int relu, const cnsn_bn_tail_t* bn2) { return add == ADD_PRE || (!bn2 && !(add == ADD_NONE && relu)); }
 }  // namespace
 
 size_t nhwc_bnhead_extra_bytes(const Plan& pl) { return bnhead_layout(nhwc_fused_geom(pl), nullptr).bytes; }
 
-int nhwc_bnhead_forward(Plan& pl, int relu, const cnsn_bn_tail_t& bn, const cnsn_bn_tail_t* bn2, const void* conv_out, const void* identity,
-                        GateDev gg, void* y, float* saved, float* bn_stats, void* workspace, size_t workspace_bytes, hipStream_t stream) {
-    if (!nhwc_bnhead_ok(pl) || !bn.training || (bn2 && !bn2->training)) return CNSN_E_UNSUPPORTED;
+int nhwc_bnhead_forward(Plan& pl, int add, int relu, const cnsn_bn_tail_t& bn, const cnsn_bn_tail_t* bn2, const void* conv_out,
+                        const void* identity, GateDev gg, void* y, float* saved, float* bn_stats, void* workspace, size_t workspace_bytes,
+                        hipStream_t stream) {
+    if (!nhwc_bnhead_ok(pl) || !bn.training || (bn2 && !bn2->training) || !bnhead_mode_ok(add, relu, bn2)) return CNSN_E_UNSUPPORTED;
+    if (add != ADD_NONE && !identity) return CNSN_E_NULL;
     const NhwcGeom ng = nhwc_fused_geom(pl);
     const BnHeadWs w = bnhead_layout(ng, workspace);
     if (workspace_bytes < w.bytes) return CNSN_E_WORKSPACE;
     NhwcBnArgs a = make_bn_args(pl, ng, relu, bn, bn2, bn_stats, w);
     a.f.slim = saved;
     if (saved) a.f.gout = saved + (size_t)SL_G * pl.P;
-    a.f.keep = keep_first_read(2, tensor_bytes(pl));
+    a.f.keep = keep_first_read(add == ADD_PRE ? 2 : 1, tensor_bytes(pl));  // (without a PRE add phase A reads conv_out alone)
     int status = CNSN_E_UNSUPPORTED;
     dispatch_t(pl.pr.dtype, [&](auto tt, auto vt) {
         using T = typename decltype(tt)::type;
@@ -206,22 +212,28 @@ int nhwc_bnhead_forward(Plan& pl, int relu, const cnsn_bn_tail_t& bn, const cnsn
             status = launch_fused(pl, kern, lds, a, a.f, w.bar, stream, (const T*)conv_out, (const T*)identity, (T*)y, gg);
         };
         if (bn2)
-            a.f.keep ? go(nhwc_bnhead_fwd_kernel<T, VEC, true, true>) : go(nhwc_bnhead_fwd_kernel<T, VEC, false, true>);
-        else
-            a.f.keep ? go(nhwc_bnhead_fwd_kernel<T, VEC, true, false>) : go(nhwc_bnhead_fwd_kernel<T, VEC, false, false>);
+            return a.f.keep ? go(nhwc_bnhead_fwd_kernel<T, VEC, true, true>) : go(nhwc_bnhead_fwd_kernel<T, VEC, false, true>);
+        with_add(add, [&](auto at) {
+            constexpr int ADD = decltype(at)::value;
+            a.f.keep ? go(nhwc_bnhead_fwd_kernel<T, VEC, true, false, ADD>) : go(nhwc_bnhead_fwd_kernel<T, VEC, false, false, ADD>);
+        });
     });
     if (knob(K_DEBUG))
-        fprintf(stderr, "[cnsn] nhwc bn-block fwd: tiles=%d (S=%d rows=%d tcb=%d) groups=%d keep=%d -> status %d\n", a.f.ntiles, ng.S,
-                ng.rows, ng.tcb, a.f.ngroups, a.f.keep, status);
+        fprintf(stderr, "[cnsn] nhwc bn-block fwd: tiles=%d (S=%d rows=%d tcb=%d) groups=%d keep=%d -> status %d mode=%s\n", a.f.ntiles,
+                ng.S, ng.rows, ng.tcb, a.f.ngroups, a.f.keep, status, add_name(add));
     return status;
 }
 
-int nhwc_bnhead_backward(Plan& pl, int relu, const cnsn_bn_tail_t& bn, const cnsn_bn_tail_t* bn2, const void* gy, const void* conv_out,
-                         const void* identity, GateDev gg, const float* saved, const float* bn_stats, void* d_conv, void* d_identity,
-                         GateGradDev dg, float* dbn_w, float* dbn_b, float* dbn2_w, float* dbn2_b, void* workspace,
+int nhwc_bnhead_backward(Plan& pl, int add, int relu, const cnsn_bn_tail_t& bn, const cnsn_bn_tail_t* bn2, const void* gy,
+                         const void* conv_out, const void* identity, GateDev gg, const float* saved, const float* bn_stats, void* d_conv,
+                         void* d_identity, GateGradDev dg, float* dbn_w, float* dbn_b, float* dbn2_w, float* dbn2_b, void* workspace,
                          size_t workspace_bytes, hipStream_t stream) {
-    if (!nhwc_bnhead_ok(pl, false) || !bn.training || (bn2 && !bn2->training)) return CNSN_E_UNSUPPORTED;
-    if (!saved || !bn_stats || !d_conv || !d_identity || !dbn_w || !dbn_b || (bn2 && (!dbn2_w || !dbn2_b))) return CNSN_E_NULL;
+    if (!nhwc_bnhead_ok(pl, false) || !bn.training || (bn2 && !bn2->training) || !bnhead_mode_ok(add, relu, bn2))
+        return CNSN_E_UNSUPPORTED;
+    // a POST add without a ReLU: the identity's gradient is grad_y itself, nothing of the identity is read or written
+    const int eff_add = (add == ADD_POST && !relu) ? ADD_NONE : add;
+    if (!saved || !bn_stats || !d_conv || !dbn_w || !dbn_b || (bn2 && (!dbn2_w || !dbn2_b))) return CNSN_E_NULL;
+    if (eff_add != ADD_NONE && (!identity || !d_identity)) return CNSN_E_NULL;
     const NhwcGeom ng = nhwc_fused_geom(pl);
     const BnHeadWs w = bnhead_layout(ng, workspace);
     if (workspace_bytes < w.bytes) return CNSN_E_WORKSPACE;
@@ -231,7 +243,7 @@ int nhwc_bnhead_backward(Plan& pl, int relu, const cnsn_bn_tail_t& bn, const cns
     a.dbn_b = dbn_b;
     a.dbn2_w = dbn2_w;
     a.dbn2_b = dbn2_b;
-    a.f.keep = keep_first_read(3, tensor_bytes(pl));
+    a.f.keep = keep_first_read(eff_add != ADD_NONE ? 3 : 2, tensor_bytes(pl));
     int status = CNSN_E_UNSUPPORTED;
     dispatch_t(pl.pr.dtype, [&](auto tt, auto vt) {
         using T = typename decltype(tt)::type;
@@ -242,13 +254,15 @@ int nhwc_bnhead_backward(Plan& pl, int relu, const cnsn_bn_tail_t& bn, const cns
                                   (T*)d_conv, (T*)d_identity, gg, dg);
         };
         if (bn2)
-            a.f.keep ? go(nhwc_bnhead_bwd_kernel<T, VEC, true, true>) : go(nhwc_bnhead_bwd_kernel<T, VEC, false, true>);
-        else
-            a.f.keep ? go(nhwc_bnhead_bwd_kernel<T, VEC, true, false>) : go(nhwc_bnhead_bwd_kernel<T, VEC, false, false>);
+            return a.f.keep ? go(nhwc_bnhead_bwd_kernel<T, VEC, true, true>) : go(nhwc_bnhead_bwd_kernel<T, VEC, false, true>);
+        with_add(eff_add, [&](auto at) {
+            constexpr int ADD = decltype(at)::value;
+            a.f.keep ? go(nhwc_bnhead_bwd_kernel<T, VEC, true, false, ADD>) : go(nhwc_bnhead_bwd_kernel<T, VEC, false, false, ADD>);
+        });
     });
     if (knob(K_DEBUG))
-        fprintf(stderr, "[cnsn] nhwc bn-block bwd: tiles=%d (S=%d rows=%d tcb=%d) groups=%d keep=%d -> status %d\n", a.f.ntiles, ng.S,
-                ng.rows, ng.tcb, a.f.ngroups, a.f.keep, status);
+        fprintf(stderr, "[cnsn] nhwc bn-block bwd: tiles=%d (S=%d rows=%d tcb=%d) groups=%d keep=%d -> status %d mode=%s\n", a.f.ntiles,
+                ng.S, ng.rows, ng.tcb, a.f.ngroups, a.f.keep, status, add_name(add));
     return status;
 }
 

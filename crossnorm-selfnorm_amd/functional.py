@@ -669,7 +669,8 @@ class FusedCNSNTail(torch.autograd.Function):
 
 
 # ------------------------------------------------------------------------------------------------
-# the block's last BatchNorm2d in front of the op: y = act(SelfNorm(BatchNorm2d(conv_out) + identity))
+# the block's last BatchNorm2d in front of the op: y = act(SelfNorm(BatchNorm2d(conv_out) + identity)), or with the identity
+# behind the op / without one (add_mode 'post' / 'none': pos='residual')
 # (cnsn_forward_bn_block / cnsn_backward_bn_block, csrc/cnsn_nhwc_bnhead_kernels.h)
 # ------------------------------------------------------------------------------------------------
 _bn_block_plan_cache = _plan_cache()
@@ -678,9 +679,10 @@ _BN_BLOCK = os.environ.get("CNSN_BN_BLOCK", "1") != "0"
 
 
 def bn_block_plan(x: torch.Tensor, cfg: FusedConfig) -> bool:
-    """True when ONE launch per direction evaluates `act(CNSN(BatchNorm2d(conv_out) + identity))` for this tensor / configuration
-    (cnsn_bn_block_plan: channels-last, SelfNorm alone with one gate in training mode, N <= 256, no stream capture) —
-    remembered per (shape, dtype, configuration, strategy)."""
+    """True when ONE launch per direction evaluates `act(CNSN(BatchNorm2d(conv_out) + identity))` — `cfg.add_mode` 'post':
+    `act(CNSN(BatchNorm2d(conv_out)) + identity)`, 'none': `CNSN(BatchNorm2d(conv_out))` without a ReLU — for this tensor /
+    configuration (cnsn_bn_block_plan: channels-last, SelfNorm alone with one gate in training mode, N <= 256, no stream
+    capture) — remembered per (shape, dtype, configuration, strategy)."""
     if not _BN_BLOCK or cfg.cn_active or not cfg.sn_training or not _single_launch_tensor(x):   # (degraded: the un-fused sequence)
         return False
 
@@ -688,14 +690,16 @@ def bn_block_plan(x: torch.Tensor, cfg: FusedConfig) -> bool:
         prob = _problem(x, cfg)
         prob.layout = _ffi.LAYOUT_NHWC
         return _ffi.lib().cnsn_bn_block_plan(C.byref(prob), C.byref(_epilogue(cfg, None))) == 1
-    return _remembered(_bn_block_plan_cache, (tuple(x.shape), x.dtype, x.device.index, cfg.relu, cfg.sn_two, _strategy), ask)
+    return _remembered(_bn_block_plan_cache, (tuple(x.shape), x.dtype, x.device.index, cfg.add_mode, cfg.relu, cfg.sn_two, _strategy),
+                       ask)
 
 
 class FusedBnBlock(torch.autograd.Function):
     """y = act(SelfNorm(BatchNorm2d(conv_out) + identity)) — the tail of a ResNet bottleneck (resnet_cnsn.py:108-122, pos='post')
     in one launch per direction; with `bn2_*` the identity is itself `BatchNorm2d(skip convolution)` (the block's downsample,
-    :99-100) and `identity` is that convolution's output.  Saves conv_out and identity (what the BatchNorm2d layers and the add
-    would have saved), never writes a BatchNorm2d's output or the sum."""
+    :99-100) and `identity` is that convolution's output.  `cfg.add_mode` 'post' / 'none' (pos='residual', :112-122):
+    y = act(SelfNorm(BatchNorm2d(conv_out)) + identity) / y = SelfNorm(BatchNorm2d(conv_out)) with `identity` None.  Saves conv_out
+    and identity (what the BatchNorm2d layers and the add would have saved), never writes a BatchNorm2d's output or the sum."""
 
     @staticmethod
     def forward(ctx, conv_out, identity, cfg: FusedConfig, g_w, g_gamma, g_beta, g_rm, g_rv, bn_w, bn_b, bn_rm, bn_rv, bn_eps,
@@ -706,7 +710,8 @@ class FusedBnBlock(torch.autograd.Function):
             lib = _ffi.lib()
             _ffi.check_resident_health("cnsn_forward_bn_block")
             x = _dense_cl(conv_out)
-            idt = _addend_like(x, identity, "cnsn_forward_bn_block", _dense_cl, "identity")
+            assert (identity is None) == (cfg.add_mode == "none")
+            idt = None if identity is None else _addend_like(x, identity, "cnsn_forward_bn_block", _dense_cl, "identity")
             prob = _problem(x, cfg)
             prob.layout = _ffi.LAYOUT_NHWC
             dev = x.device
@@ -745,7 +750,10 @@ class FusedBnBlock(torch.autograd.Function):
             gy = _grad_like(gy, x, True)
             hs = head.struct()
             ss = skip.struct() if skip else None
-            d_conv, d_idt = _out_like(x), _out_like(x)
+            # the identity's gradient: written by the launch, except behind the op without a ReLU, where it is grad_y itself
+            writes_idt = cfg.add_mode == "pre" or (cfg.add_mode == "post" and cfg.relu)
+            d_conv = _out_like(x)
+            d_idt = _out_like(x) if writes_idt else (gy if cfg.add_mode == "post" else None)
             grads, gg = _gate_grad_views(x.shape[1], dev, 4)
             dbw, dbb, d2w, d2b = grads[3:]
             ws_bytes = _sizes(prob)[1]
@@ -755,7 +763,8 @@ class FusedBnBlock(torch.autograd.Function):
             ws = _workspace(ws_bytes, dev)
             epi = _epilogue(cfg, idt)
             st = lib.cnsn_backward_bn_block(C.byref(prob), C.byref(epi), C.byref(hs), C.byref(ss) if ss else None, _ptr(gy), _ptr(x),
-                                            C.byref(gate.c), _ptr(saved), _ptr(stats), _ptr(d_conv), _ptr(d_idt), C.byref(gg),
+                                            C.byref(gate.c), _ptr(saved), _ptr(stats), _ptr(d_conv), _ptr(d_idt) if writes_idt else None,
+                                            C.byref(gg),
                                             _ptr(dbw), _ptr(dbb), _ptr(d2w) if skip else None, _ptr(d2b) if skip else None, _ptr(ws),
                                             ws_bytes, _stream(x))
             _ffi.check(st, "cnsn_backward_bn_block")

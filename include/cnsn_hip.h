@@ -323,6 +323,17 @@ int cnsn_sn_cluster_plan(const cnsn_problem_t* prob, const cnsn_epilogue_t* epi,
  *   - channels-last layout, SelfNorm alone (cn_active = 0, one gate), training mode in BOTH normalisations, N <= 256;
  *     epilogue: add_mode PRE with addend = identity (sum_out NULL), relu 0 / 1.  Anything else — cnsn_bn_block_plan() == 0 —
  *     returns CNSN_E_UNSUPPORTED: the caller then runs BatchNorm2d itself and cnsn_forward_fused, as the reference does.
+ *   - epilogue add_mode POST / NONE (additive, same ABI version): the block's tail at pos='residual' (resnet_cnsn.py:112-122,
+ *     `out = self.bn3(out); out = self.cnsn(out); out += identity; out = self.relu(out)`),
+ *       POST   y = act( CNSN( BatchNorm2d(conv_out) ) + identity ),  relu 0 / 1
+ *       NONE   y = CNSN( BatchNorm2d(conv_out) ),                    relu 0 only, addend ignored (what stands in front of the
+ *              InstanceNorm2d of an IBN-b block, resnet_ibn_cnsn.py:109-127)
+ *     The op's input is bn3's output alone: the statistics phase reads conv_out only, the identity is added behind the gate
+ *     (one rounding of g*x + identity, where cnsn_forward_fused's POST add rounds it) — 4 + 8 tensor passes (POST with the
+ *     ReLU), 3 + 5 (NONE) where BatchNorm2d and the op as separate calls move 8 + 12 / 8 + 8.  Same conditions, buffers and
+ *     sizes as PRE; bn_skip must be NULL (CNSN_E_UNSUPPORTED otherwise).  Backward: grad_identity is written for POST with
+ *     relu 1 (grad_y behind the ReLU mask) and not touched otherwise (may be NULL): without the ReLU the identity's gradient
+ *     is grad_y itself.
  *   - bn: BatchNorm2d's parameters and buffers (the struct of the fused tail); running statistics and num_batches_tracked are
  *     updated by the forward as nn.BatchNorm2d does (momentum; running_var takes the unbiased variance).
  *   - bn_skip (may be NULL): the skip path ends in a BatchNorm2d of its own — the block's `downsample` (resnet_cnsn.py:99-100,
