@@ -235,10 +235,7 @@ __global__ __launch_bounds__(kBlock, CNSN_NHWC_WG_PER_CU) void nhwc_bnact_fwd_ke
                 const double m2 = s2 - s1 * s1 * a.inv_r;
                 const double var = (m2 > 0.0 ? m2 : 0.0) * a.inv_r;  // biased: what normalises (torch)
                 const double rstd = 1.0 / sqrt(var + (double)a.bn.eps);
-                const double mom = (double)a.bn.momentum;
-                a.bn.run_mean[c] = (float)((1.0 - mom) * (double)a.bn.run_mean[c] + mom * mean);
-                a.bn.run_var[c] = (float)((1.0 - mom) * (double)a.bn.run_var[c] + mom * var * a.unbias_r);
-                if (c == 0) bump_batches_tracked(a.bn.nbt);
+                running_update(a.bn.run_mean, a.bn.run_var, a.bn.nbt, c, mean, var, a.unbias_r, (double)a.bn.momentum);
                 o_m[q] = (float)mean;
                 o_r[q] = (float)rstd;
             }

@@ -106,16 +106,6 @@ __device__ __forceinline__ void nhwc_rows_sum_part(const NhwcGeom& g, const Nhwc
     __syncthreads();  // (the staging area is the next call's)
 }
 
-// the lane's value of a per-channel array in phase B: thread j < GC owns channel c0 + j
-template <int GC>
-__device__ __forceinline__ double pick(const double (&v)[GC], int j) {
-    double r = 0.0;
-#pragma unroll
-    for (int q = 0; q < GC; ++q)
-        if (q == j) r = v[q];
-    return r;
-}
-
 // x = T(alpha*c + beta): a BatchNorm2d's output, rounded where the layer stores it
 template <typename T>
 __device__ __forceinline__ float bn_out(float c, float alpha, float beta) {

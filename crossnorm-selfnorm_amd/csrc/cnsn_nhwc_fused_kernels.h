@@ -39,6 +39,7 @@
 // kernels), so any forward still feeds any backward.
 #pragma once
 #include "cnsn_nhwc_kernels.h"
+#include "cnsn_nhwc_phase_b.h"
 #include "cnsn_resident_kernels.h"
 
 #ifndef CNSN_NHWC_GC
@@ -309,15 +310,8 @@ __global__ __launch_bounds__(kBlock, CNSN_NHWC_WG_PER_CU) void nhwc_fused_fwd_ke
 #pragma unroll
             for (int j = 0; j < GC; ++j) rstd[j] = 1.0 / sqrt(s2[j] * a.inv_n + (double)a.eps_bn);
             if (threadIdx.x < GC) {
-                const int j = threadIdx.x, c = c0 + j;
-                double vj = 0.0, mj = 0.0;
-#pragma unroll
-                for (int q = 0; q < GC; ++q)
-                    if (q == j) vj = s2[q] * a.inv_n, mj = mz[q];
-                const double mom = a.momentum;
-                gg.run_mean[c] = (float)((1.0 - mom) * gg.run_mean[c] + mom * mj);
-                gg.run_var[c] = (float)((1.0 - mom) * gg.run_var[c] + mom * vj * a.unbias_n);
-                if (c == 0) bump_batches_tracked(gg.nbt);
+                const int j = threadIdx.x;
+                running_update(gg.run_mean, gg.run_var, gg.nbt, c0 + j, pick<GC>(mz, j), pick<GC>(s2, j) * a.inv_n, a.unbias_n, a.momentum);
             }
         } else {
 #pragma unroll
@@ -326,13 +320,7 @@ __global__ __launch_bounds__(kBlock, CNSN_NHWC_WG_PER_CU) void nhwc_fused_fwd_ke
                 rstd[j] = 1.0 / sqrt((double)gg.run_var[c0 + j] + (double)a.eps_bn);
             }
         }
-        if (a.slim && threadIdx.x < GC) {
-            double rj = 0.0;
-#pragma unroll
-            for (int q = 0; q < GC; ++q)
-                if (q == (int)threadIdx.x) rj = rstd[q];
-            slim_rstd(a.slim, g.P)[c0 + threadIdx.x] = rj;
-        }
+        if (a.slim && threadIdx.x < GC) slim_rstd(a.slim, g.P)[c0 + threadIdx.x] = pick<GC>(rstd, (int)threadIdx.x);
         if (live) {
             float o_g[GC], o_zh[GC], o_hi[GC], o_lo[GC], o_sig[GC];
 #pragma unroll
@@ -505,12 +493,8 @@ __global__ __launch_bounds__(kBlock, CNSN_NHWC_WG_PER_CU) void nhwc_fused_bwd_ke
         }
         block_sum_d<2 * GC>(acc, red);
         if (threadIdx.x < GC) {
-            double sd = 0.0, sdz = 0.0;
-#pragma unroll
-            for (int q = 0; q < GC; ++q)
-                if (q == (int)threadIdx.x) sd = acc[q], sdz = acc[GC + q];
-            dg.dgamma[c0 + threadIdx.x] = (float)sdz;
-            dg.dbeta[c0 + threadIdx.x] = (float)sd;
+            dg.dgamma[c0 + threadIdx.x] = (float)pick<2 * GC>(acc, GC + (int)threadIdx.x);
+            dg.dbeta[c0 + threadIdx.x] = (float)pick<2 * GC>(acc, (int)threadIdx.x);
         }
         double dz[GC];
         const double M = (double)g.M;
@@ -532,12 +516,8 @@ __global__ __launch_bounds__(kBlock, CNSN_NHWC_WG_PER_CU) void nhwc_fused_bwd_ke
         }
         block_sum_d<2 * GC>(acc, red);
         if (threadIdx.x < GC) {
-            double w0 = 0.0, w1 = 0.0;
-#pragma unroll
-            for (int q = 0; q < GC; ++q)
-                if (q == (int)threadIdx.x) w0 = acc[q], w1 = acc[GC + q];
-            dg.dw[2 * (c0 + threadIdx.x)] = (float)w0;
-            dg.dw[2 * (c0 + threadIdx.x) + 1] = (float)w1;
+            dg.dw[2 * (c0 + threadIdx.x)] = (float)pick<2 * GC>(acc, (int)threadIdx.x);
+            dg.dw[2 * (c0 + threadIdx.x) + 1] = (float)pick<2 * GC>(acc, GC + (int)threadIdx.x);
         }
         if (live) {
             const CohBuf cb(a.coefb);  // (phase C' reads them)
