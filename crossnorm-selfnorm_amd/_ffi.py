@@ -174,6 +174,46 @@ SIGNATURES = {
                                      C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]),
 }
 
+CNSN_F64 = 3
+
+
+class F64Scalars(C.Structure):
+    """cnsn_f64_scalars_t"""
+    _fields_ = [("struct_bytes", C.c_int32), ("reserved", C.c_int32), ("lam", C.c_double), ("eps_cn", C.c_double),
+                ("eps_sn", C.c_double), ("eps_bn", C.c_double), ("momentum", C.c_double)]
+
+
+class GateF64(C.Structure):
+    """cnsn_gate_f64_t"""
+    _fields_ = [("struct_bytes", C.c_int32), ("reserved", C.c_int32), ("fc_weight", C.c_void_p), ("bn_weight", C.c_void_p),
+                ("bn_bias", C.c_void_p), ("running_mean", C.c_void_p), ("running_var", C.c_void_p),
+                ("num_batches_tracked", C.c_void_p)]
+
+
+class GateGradF64(C.Structure):
+    """cnsn_gate_grad_f64_t"""
+    _fields_ = [("struct_bytes", C.c_int32), ("reserved", C.c_int32), ("d_fc_weight", C.c_void_p), ("d_bn_weight", C.c_void_p),
+                ("d_bn_bias", C.c_void_p)]
+
+
+# the float64 entry points of include/cnsn_hip.h (bound and symbol-checked by lib() like the ones above)
+SIGNATURES_F64 = {
+    "cnsn_workspace_bytes_f64": (C.c_size_t, [C.POINTER(Problem)]),
+    "cnsn_forward_f64": (C.c_int, [C.POINTER(Problem), C.POINTER(F64Scalars), C.c_void_p, C.c_void_p, C.c_void_p,
+                                   C.POINTER(GateF64), C.POINTER(GateF64), C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t,
+                                   C.c_void_p]),
+    "cnsn_backward_f64": (C.c_int, [C.POINTER(Problem), C.POINTER(F64Scalars), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                    C.POINTER(GateF64), C.POINTER(GateF64), C.c_void_p, C.c_void_p, C.POINTER(GateGradF64),
+                                    C.POINTER(GateGradF64), C.c_void_p, C.c_size_t, C.c_void_p]),
+    "cnsn_plane_stats_f64": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int32), C.c_double,
+                                       C.c_void_p, C.c_void_p]),
+    "cnsn_plane_stats_backward_f64": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int32),
+                                                C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "cnsn_plane_affine_f64": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p,
+                                        C.c_void_p]),
+    "cnsn_plane_dot_f64": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
+}
+
 _lib = None
 
 
@@ -191,7 +231,7 @@ def lib():
                 "Run `python __graft_entry__.py` (hipcc --offload-arch=gfx950). There is no "
                 "CPU or eager fallback.")
         handle = C.CDLL(LIB_PATH)
-        for name, (res, args) in SIGNATURES.items():
+        for name, (res, args) in (*SIGNATURES.items(), *SIGNATURES_F64.items()):
             fn = getattr(handle, name)  # AttributeError if the .so lacks a declared symbol
             fn.restype, fn.argtypes = res, args
         got = handle.cnsn_abi_version()

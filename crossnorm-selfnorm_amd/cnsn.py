@@ -44,13 +44,16 @@ def calc_ins_mean_std(x, eps=1e-5):
     """Per-(n,c) mean and sqrt(unbiased variance + eps) over H*W, each shaped (N,C,1,1)
     (reference models/cnsn.py:8-17).  Differentiable.
 
-    float64 (the reference takes any floating dtype, :12-16): the parameter-free ops — this one, `instance_norm_mix`,
-    `cn_op_2ins_space_chan` / `CrossNorm` — accept it, compute on a float32 copy with the float32 kernels (whose plane
-    statistics and scalar algebra are fp32 / fp64 as for any input) and return float64: float32 ACCURACY in a float64
-    container, differentiable through the two casts.  So do `SelfNorm` and `CNSN` (round 6; models/cnsn.py:130-150 takes any
-    floating dtype): float64 activations go through the float32 kernels, the gate's parameters — float32 or, after
-    `module.double()`, float64 — are read as float32 and get gradients in their own dtype."""
+    float64 (the reference takes any floating dtype, :12-16): a float64 tensor on the device is computed by the float64
+    kernels (`functional.f64_native`; csrc/cnsn_f64_kernels.h) — this function, `instance_norm_mix`,
+    `cn_op_2ins_space_chan` / `CrossNorm`, `SelfNorm` and `CNSN`: elements, statistics, the gate's parameters (a float32
+    module's as double copies; after `module.double()` as they are), running statistics and gradients are float64
+    throughout, so `torch.autograd.gradcheck` applies.  CNSN_F64_NATIVE=0 restores the route of round 6 for A/B runs, and the
+    BatchNorm2d tails, IBN, `bn_act` and a SelfNorm composed around nn.SyncBatchNorm still take it: a float32 copy through
+    the float32 kernels, returned as float64 — float32 ACCURACY in a float64 container."""
     assert x.dim() == 4
+    if _F.f64_native(x):
+        return _F.PlaneStatsF64.apply(x, float(eps), None)
     if _is_f64(x):
         mean, std = _F.PlaneStats.apply(x.float(), float(eps), None, True)
         return mean.double(), std.double()
@@ -60,6 +63,11 @@ def calc_ins_mean_std(x, eps=1e-5):
 def instance_norm_mix(content_feat, style_feat):
     """Give `content_feat` the plane statistics of `style_feat` (reference models/cnsn.py:20-29)."""
     assert content_feat.size()[:2] == style_feat.size()[:2]
+    if _F.f64_native(content_feat) and _F.f64_native(style_feat):
+        s_mean, s_std = calc_ins_mean_std(style_feat)
+        c_mean, c_std = calc_ins_mean_std(content_feat)
+        scale = s_std / c_std
+        return _F.PlaneAffineF64.apply(content_feat, scale, s_mean - c_mean * scale)
     if _is_f64(content_feat):
         return instance_norm_mix(content_feat.float(), style_feat.float()).double()
     s_mean, s_std = calc_ins_mean_std(style_feat)
@@ -123,7 +131,7 @@ def cn_op_2ins_space_chan(x, crop='neither', beta=1, bbx_thres=0.1, lam=None, ch
     assert crop in _CROPS
     if draws is None:
         draws = draw_cn(x.size(), crop, beta, bbx_thres, chan)
-    if _is_f64(x):   # (see calc_ins_mean_std)
+    if _is_f64(x) and not _F.f64_native(x):   # (see calc_ins_mean_std)
         return _F.fused_cnsn(x.float(), _cn_config(draws, lam), perm=draws.perm, chan_perm=draws.chan_perm).double()
     return _F.fused_cnsn(x, _cn_config(draws, lam), perm=draws.perm, chan_perm=draws.chan_perm)
 
@@ -278,7 +286,7 @@ class SelfNorm(nn.Module):
         return kw, None, None
 
     def forward(self, x):
-        if _is_f64(x):     # (float32 accuracy in a float64 container: see calc_ins_mean_std)
+        if _is_f64(x) and not (_F.f64_native(x) and self._fusable()):     # (the float-copy route: see calc_ins_mean_std)
             return self.forward(x.float()).double()
         if not self._fusable():
             return self._forward_composed(x)
@@ -296,7 +304,7 @@ class CNSN(nn.Module):
         self.selfnorm = selfnorm
 
     def forward(self, x):
-        if _is_f64(x):
+        if _is_f64(x) and not _F.f64_native(x):
             return self.forward(x.float()).double()
         cn, sn = self.crossnorm, self.selfnorm
         fuse = (cn is not None and sn is not None and type(cn) is CrossNorm and type(sn) is SelfNorm and sn._fusable()
@@ -323,6 +331,13 @@ class CNSN(nn.Module):
         RNG draws, `active` reset and BatchNorm1d book-keeping are those of `forward`."""
         assert add_mode in ("none", "pre", "post")
         assert (addend is None) == (add_mode == "none")
+        if _F.f64_native(x):     # the float64 kernels have no epilogue: torch's add and relu around them are exact in double
+            if add_mode == "pre":
+                x = x + addend
+            x = self.forward(x)
+            if add_mode == "post":
+                x = x + addend
+            return torch.relu(x) if relu else x
         if _is_f64(x):
             return self.forward_block(x.float(), None if addend is None else addend.float(), add_mode, relu).double()
         cn, sn = self.crossnorm, self.selfnorm

@@ -9,7 +9,9 @@
 #pragma once
 #include "cnsn_device.h"
 
-#define CNSN_ALGEBRA_FN template <typename R> __device__ __forceinline__
+// A: the launch's scalar block: MidArgs, or the float64 path's MidArgsD (the same fields with double scalars,
+// cnsn_f64_kernels.h).  S (fwd_coefs, bwd_coefs): the type the apply coefficients are stored in.
+#define CNSN_ALGEBRA_FN template <typename R, typename A = MidArgs> __device__ __forceinline__
 
 namespace cnsn {
 
@@ -70,7 +72,7 @@ __device__ __forceinline__ float div_r(float a, float b) { return a * __builtin_
 // CrossNorm algebra of one plane: own moments + the style source's style-box moments
 // (cnsn.py:24-29 folded with the box paste :75-82 and the lam blend :87), then the post-CrossNorm
 // whole-plane moments by Chan's merge, which is what SelfNorm's calc_ins_mean_std (:133) would see.
-CNSN_ALGEBRA_FN FwdPlaneT<R> fwd_plane(const MidArgs& a, const MomentsT<R>& o, R mu_sq, R M2_sq) {
+CNSN_ALGEBRA_FN FwdPlaneT<R> fwd_plane(const A& a, const MomentsT<R>& o, R mu_sq, R M2_sq) {
     const R M = a.M, Mc = a.Mc, Mo = a.M - a.Mc, lam = a.lam;
     FwdPlaneT<R> p;
     p.mu_c = o.mu_c;
@@ -99,26 +101,29 @@ CNSN_ALGEBRA_FN FwdPlaneT<R> fwd_plane(const MidArgs& a, const MomentsT<R>& o, R
 CNSN_ALGEBRA_FN R sigmoid_r(R t) { return div_r(R(1), R(1) + exp_r(-t)); }
 __device__ __forceinline__ double sigmoid_d(double t) { return sigmoid_r<double>(t); }
 
-struct FwdCoefs {
-    float a_in, xr, b_in, a_out, b_out;
+template <typename S>
+struct FwdCoefsT {
+    S a_in, xr, b_in, a_out, b_out;
 };
+using FwdCoefs = FwdCoefsT<float>;
 
 // y = a_in*(x - xr) + b_in inside the content box, a_out*x + b_out outside
-CNSN_ALGEBRA_FN FwdCoefs fwd_coefs(const MidArgs& a, const FwdPlaneT<R>& p, R g, R f) {
-    FwdCoefs c;
+template <typename R, typename S = float, typename A = MidArgs>
+__device__ __forceinline__ FwdCoefsT<S> fwd_coefs(const A& a, const FwdPlaneT<R>& p, R g, R f) {
+    FwdCoefsT<S> c;
     const R shift = a.sn_two ? p.mu_p * (f - g) : R(0);  // x*g + mean*(f-g)  (cnsn.py:148)
     if (a.cn_active) {
-        // evaluated as A*(x - xr) + B with xr = float(mu_c): the rounding of xr is folded into B
-        c.xr = (float)p.mu_c;
-        c.a_in = (float)(g * p.a1);
-        c.b_in = (float)(g * p.m_in + shift + g * p.a1 * ((R)c.xr - p.mu_c));
+        // evaluated as A*(x - xr) + B with xr = S(mu_c): the rounding of xr is folded into B (none when S is double)
+        c.xr = (S)p.mu_c;
+        c.a_in = (S)(g * p.a1);
+        c.b_in = (S)(g * p.m_in + shift + g * p.a1 * ((R)c.xr - p.mu_c));
     } else {  // SelfNorm alone: y = g*x (+ shift), one rounding like the reference's x*g (:150)
-        c.xr = 0.f;
-        c.a_in = (float)g;
-        c.b_in = (float)shift;
+        c.xr = S(0);
+        c.a_in = (S)g;
+        c.b_in = (S)shift;
     }
-    c.a_out = (float)g;
-    c.b_out = (float)shift;
+    c.a_out = (S)g;
+    c.b_out = (S)shift;
     return c;
 }
 
@@ -143,7 +148,7 @@ CNSN_ALGEBRA_FN BwdSumsT<R> fix_sums(const MidArgs& a, float s1i, float s2i, flo
 }
 
 // dL/d(pre-sigmoid) of both gates for one plane
-CNSN_ALGEBRA_FN void gate_dt(const MidArgs& a, const BwdSumsT<R>& s, R a1, R m_in, R mu_o, R mu_p, R g, R f, R& dtg,
+CNSN_ALGEBRA_FN void gate_dt(const A& a, const BwdSumsT<R>& s, R a1, R m_in, R mu_o, R mu_p, R g, R f, R& dtg,
                              R& dtf) {
     const R S1 = s.S1in + s.S1out;
     const R GdotU = a1 * s.S2in + m_in * s.S1in + s.S2out + mu_o * s.S1out;  // sum G*u
@@ -170,7 +175,7 @@ using BwdPlane = BwdPlaneT<double>;
 
 // dz = gamma*rstd*(dt - mean(dt) - zh*mean(dt*zh)) cancels catastrophically when the batch is small
 // or the gate saturated: that line is always evaluated in double, whatever R is.
-CNSN_ALGEBRA_FN BwdPlaneT<R> bwd_plane(const MidArgs& a, const BnBwd& b, const BwdSumsT<R>& s, double dtg, double dtf,
+CNSN_ALGEBRA_FN BwdPlaneT<R> bwd_plane(const A& a, const BnBwd& b, const BwdSumsT<R>& s, double dtg, double dtf,
                                        double zhg, double zhf, R g, R f, R aa, R a1, R m_in, R mu_p, R sig_p, R sig_c,
                                        R M2c) {
     const R M = a.M, Mc = a.Mc, lam = a.lam;
@@ -203,14 +208,17 @@ CNSN_ALGEBRA_FN BwdPlaneT<R> bwd_plane(const MidArgs& a, const BnBwd& b, const B
     return o;
 }
 
-struct BwdCoefs {
-    float cG_in, cX_in, xr_in, c0_in, cG_out, cX_out, xr_out, c0_out, eS, xs, e0;
+template <typename S>
+struct BwdCoefsT {
+    S cG_in, cX_in, xr_in, c0_in, cG_out, cX_out, xr_out, c0_out, eS, xs, e0;
 };
+using BwdCoefs = BwdCoefsT<float>;
 
 // dx = cG*G + cX*(x - xr) + c0 by region, + eS*(x - xs) + e0 inside the style box.
 // (Emu_in, Esig_in) = what the plane that borrowed THIS plane's statistics sends back.
-CNSN_ALGEBRA_FN BwdCoefs bwd_coefs(const MidArgs& a, const BwdPlaneT<R>& o, R Emu_in, R Esig_in, R g, R a1, R m_in,
-                                   R mu_p, double mu_c, R sig_c, double mu_s, R sig_s) {
+template <typename R, typename S = float, typename A = MidArgs>
+__device__ __forceinline__ BwdCoefsT<S> bwd_coefs(const A& a, const BwdPlaneT<R>& o, R Emu_in, R Esig_in, R g, R a1, R m_in,
+                                                  R mu_p, double mu_c, R sig_c, double mu_s, R sig_s) {
     const R M = a.M, Mc = a.Mc, Ms = a.Ms;
     R cX_in = a1 * a1 * o.k, c0_in = a1 * (div_r(o.dmu_p, M) + o.k * (m_in - mu_p));
     R eS = R(0), e0 = R(0);
@@ -224,19 +232,19 @@ CNSN_ALGEBRA_FN BwdCoefs bwd_coefs(const MidArgs& a, const BwdPlaneT<R>& o, R Em
         cX_in += eS;
         c0_in += e0;
     }
-    // evaluated as c*(x - float(ref)) + c0: the rounding of each reference point is folded into c0
-    BwdCoefs c;
-    c.xr_in = (float)mu_c;
-    c.cG_in = (float)(a1 * g);
-    c.cX_in = (float)cX_in;
-    c.c0_in = (float)(c0_in + cX_in * (R)((double)c.xr_in - mu_c));
-    c.xr_out = (float)mu_p;
-    c.xs = (float)mu_s;
-    c.cG_out = (float)g;
-    c.cX_out = (float)o.k;
-    c.c0_out = (float)(div_r(o.dmu_p, M) + o.k * ((R)c.xr_out - mu_p));
-    c.eS = (float)eS;
-    c.e0 = (float)(e0 + eS * (R)((double)c.xs - mu_s));
+    // evaluated as c*(x - S(ref)) + c0: the rounding of each reference point is folded into c0
+    BwdCoefsT<S> c;
+    c.xr_in = (S)mu_c;
+    c.cG_in = (S)(a1 * g);
+    c.cX_in = (S)cX_in;
+    c.c0_in = (S)(c0_in + cX_in * (R)((double)c.xr_in - mu_c));
+    c.xr_out = (S)mu_p;
+    c.xs = (S)mu_s;
+    c.cG_out = (S)g;
+    c.cX_out = (S)o.k;
+    c.c0_out = (S)(div_r(o.dmu_p, M) + o.k * ((R)c.xr_out - mu_p));
+    c.eS = (S)eS;
+    c.e0 = (S)(e0 + eS * (R)((double)c.xs - mu_s));
     return c;
 }
 

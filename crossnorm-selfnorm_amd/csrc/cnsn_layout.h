@@ -88,8 +88,8 @@ struct CnRowsT {
     R mu_o, M2c, sig_c, sig_s, aa, a1, m_in;
     double mu_s;
 };
-template <typename R>
-__device__ __forceinline__ CnRowsT<R> load_cn_rows(const MidArgs& a, const double* __restrict__ saved, SvRec p,
+template <typename R, typename A = MidArgs>
+__device__ __forceinline__ CnRowsT<R> load_cn_rows(const A& a, const double* __restrict__ saved, SvRec p,
                                                    double mu_c) {
     CnRowsT<R> r;
     if (a.cn_active) {

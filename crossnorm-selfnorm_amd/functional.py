@@ -821,6 +821,8 @@ def fused_cnsn(x, cfg: FusedConfig, perm=None, chan_perm=None, g: Optional[GateP
     fa = (f.fc_weight, f.bn_weight, f.bn_bias, f.running_mean, f.running_var) if f else (None,) * 5
     g_nbt = g.num_batches_tracked if (g and cfg.sn_training) else None
     f_nbt = f.num_batches_tracked if (f and cfg.sn_training) else None
+    if x.dtype == torch.float64:      # the float64 kernels (functional_f64.py); callers send only `f64_native` tensors here
+        return fused_cnsn_f64(x, cfg, perm, chan_perm, g, f)
     glue = _ffi.glue()
     if glue is None:
         return FusedCNSN.apply(x, cfg, perm, chan_perm, *ga, *fa, addend, g_nbt, f_nbt)
@@ -1226,3 +1228,8 @@ class JsdConsistency(torch.autograd.Function):
 
 def jsd_consistency(logits_clean, logits_aug1, logits_aug2):
     return JsdConsistency.apply(logits_clean, logits_aug1, logits_aug2)
+
+
+# float64: sibling Functions over the cnsn_*_f64 entry points (imported last: that module uses the helpers above)
+from .functional_f64 import (FusedCNSNF64, PlaneAffineF64, PlaneStatsF64, f64_native, f64_native_enabled,  # noqa: E402,F401
+                             fused_cnsn_f64)

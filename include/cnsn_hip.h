@@ -9,7 +9,8 @@
  * Conventions
  *   - Plain C: pointers, sizes, PODs.  No C++ types, no torch types.
  *   - Every pointer is a DEVICE pointer unless it says "host".  Activations are NCHW, contiguous,
- *     16-byte aligned, element type `dtype`.  All per-plane / per-channel side arrays are float32.
+ *     16-byte aligned, element type `dtype`.  All per-plane / per-channel side arrays are float32 (float64 in the *_f64
+ *     entry points at the end of this header).
  *   - The caller owns every buffer the op's entry points take (inputs, outputs, `saved`, `workspace`, `context`); those
  *     entry points enqueue their work on `stream` (a hipStream_t passed as void*; NULL = default stream), never
  *     synchronise the host and never throw.  What the library DOES own, allocate and keep — all of it outside the
@@ -48,10 +49,10 @@ extern "C" {
 /* Largest batch whose permutation can travel as a launch argument (cnsn_problem_t.perm_host). */
 #define CNSN_PERM_INLINE_MAX 1024
 
-/* Element types of the activation tensors.  float64 is NOT offered here (the reference's eager path accepts any float tensor,
- * models/cnsn.py:12-16): CNSN_E_DTYPE.  The Python layer takes float64 tensors through these entry points on a float32 copy
- * and returns float64 (float32 accuracy in a float64 container: cnsn_amd/cnsn.py). */
-enum cnsn_dtype { CNSN_F32 = 0, CNSN_BF16 = 1, CNSN_F16 = 2 };
+/* Element types of the activation tensors.  CNSN_F64 (the reference's eager path accepts any float tensor,
+ * models/cnsn.py:12-16) is taken by the *_f64 entry points at the end of this header and by nothing else: every other entry
+ * point answers CNSN_E_DTYPE for it. */
+enum cnsn_dtype { CNSN_F32 = 0, CNSN_BF16 = 1, CNSN_F16 = 2, CNSN_F64 = 3 };
 
 enum cnsn_status {
     CNSN_OK = 0,
@@ -622,6 +623,67 @@ size_t cnsn_jsd_workspace_bytes(int B);
 int cnsn_jsd(const void* logits_clean, const void* logits_aug1, const void* logits_aug2, int dtype, int B,
              int K, float* loss, void* d_clean, void* d_aug1, void* d_aug2, void* workspace,
              size_t workspace_bytes, void* stream);
+
+/* ---- float64 (additive; the ABI number stays) -------------------------------------------------------------------------------
+ * The op and the per-plane primitives for `double` tensors: elements, plane statistics, every side array, the gate's
+ * parameters, running statistics and parameter gradients are all float64, and so is the arithmetic (csrc/cnsn_f64_kernels.h).
+ * What it is for: a model moved to .double() to chase a numerical problem, torch.autograd.gradcheck, and holding the backward
+ * algebra to 1e-10 on the device.  Always the two-pass streaming kernels (cnsn_problem_t.strategy, context and perm_host are
+ * ignored): plain launches, no persistent grid, capturable into a graph.  Same rules as the float entry points: caller-owned
+ * buffers, stream-ordered, status codes, nothing launched on an argument error.
+ *   - prob->dtype must be CNSN_F64 (else CNSN_E_DTYPE); prob->layout must be CNSN_LAYOUT_NCHW (else CNSN_E_UNSUPPORTED: the
+ *     caller copies to NCHW, as the reference does); there is no epilogue.  The float fields lam, eps_cn, eps_sn, eps_bn and
+ *     momentum of cnsn_problem_t are NOT read: float(0.3) is 1e-8 away from 0.3.  They travel in cnsn_f64_scalars_t.
+ *   - `saved`: as for cnsn_forward — the common record already holds doubles.  Its size depends on N and C alone:
+ *     cnsn_saved_floats() of the same problem with dtype CNSN_F32.  workspace: cnsn_workspace_bytes_f64().
+ *   - any N >= 1 (training mode: N >= 2, CNSN_E_BATCH), crop boxes, lam, channel permutation, one or two gates, training
+ *     (running statistics and num_batches_tracked updated in the launch) and eval. */
+typedef struct cnsn_f64_scalars {
+    int32_t struct_bytes; /* = sizeof(cnsn_f64_scalars_t) */
+    int32_t reserved;
+    double lam;      /* 0 when lam is None */
+    double eps_cn;   /* 1e-5  */
+    double eps_sn;   /* 1e-12 */
+    double eps_bn;   /* 1e-5  */
+    double momentum; /* 0.1   */
+} cnsn_f64_scalars_t;
+
+typedef struct cnsn_gate_f64 {
+    int32_t struct_bytes;    /* = sizeof(cnsn_gate_f64_t) */
+    int32_t reserved;
+    const double* fc_weight; /* (C,2) */
+    const double* bn_weight; /* (C)   */
+    const double* bn_bias;   /* (C)   */
+    double* running_mean;    /* (C) updated in place when sn_training */
+    double* running_var;     /* (C) */
+    int64_t* num_batches_tracked; /* int64 scalar or NULL: += 1 by the forward when sn_training */
+} cnsn_gate_f64_t;
+
+typedef struct cnsn_gate_grad_f64 {
+    int32_t struct_bytes; /* = sizeof(cnsn_gate_grad_f64_t) */
+    int32_t reserved;
+    double* d_fc_weight;  /* (C,2) written (not accumulated) */
+    double* d_bn_weight;  /* (C) */
+    double* d_bn_bias;    /* (C) */
+} cnsn_gate_grad_f64_t;
+
+size_t cnsn_workspace_bytes_f64(const cnsn_problem_t* prob);
+int cnsn_forward_f64(const cnsn_problem_t* prob, const cnsn_f64_scalars_t* scalars, const double* x, const int64_t* perm,
+                     const int64_t* chan_perm, const cnsn_gate_f64_t* g, const cnsn_gate_f64_t* f, double* y, float* saved,
+                     void* workspace, size_t workspace_bytes, void* stream);
+int cnsn_backward_f64(const cnsn_problem_t* prob, const cnsn_f64_scalars_t* scalars, const double* grad_y, const double* x,
+                      const int64_t* perm, const int64_t* chan_perm, const cnsn_gate_f64_t* g, const cnsn_gate_f64_t* f,
+                      const float* saved, double* grad_x, const cnsn_gate_grad_f64_t* dg, const cnsn_gate_grad_f64_t* df,
+                      void* workspace, size_t workspace_bytes, void* stream);
+/* cnsn_plane_stats / _backward / cnsn_plane_affine / cnsn_plane_dot for double tensors: mean_std (2, N*C), mean / std / dmean /
+ * dstd / scale / shift (N*C) and sums (2, N*C) are float64 */
+int cnsn_plane_stats_f64(const double* x, int N, int C, int H, int W, const int32_t* box, double eps, double* mean_std,
+                         void* stream);
+int cnsn_plane_stats_backward_f64(const double* x, int N, int C, int H, int W, const int32_t* box, const double* mean,
+                                  const double* std, const double* dmean, const double* dstd, double* dx, void* stream);
+int cnsn_plane_affine_f64(const double* x, int N, int C, int H, int W, const double* scale, const double* shift, double* y,
+                          void* stream);
+int cnsn_plane_dot_f64(const double* g, const double* x, int N, int C, int H, int W, double* sums, void* stream);
 
 #ifdef __cplusplus
 }
