@@ -45,7 +45,7 @@ def calc_ins_mean_std(x, eps=1e-5):
     (reference models/cnsn.py:8-17).  Differentiable.
 
     float64 (the reference takes any floating dtype, :12-16): a float64 tensor on the device is computed by the float64
-    kernels (`functional.f64_native`; csrc/cnsn_f64_kernels.h) — this function, `instance_norm_mix`,
+    kernels (`functional.f64_native`; csrc/cnsn_stream_kernels.h for `double`) — this function, `instance_norm_mix`,
     `cn_op_2ins_space_chan` / `CrossNorm`, `SelfNorm` and `CNSN`: elements, statistics, the gate's parameters (a float32
     module's as double copies; after `module.double()` as they are), running statistics and gradients are float64
     throughout, so `torch.autograd.gradcheck` applies.  CNSN_F64_NATIVE=0 restores the route of round 6 for A/B runs, and the

@@ -50,17 +50,17 @@ static int mid_block(const cnsn_problem_t& p, int tile) {
     do {                                                                                             \
         const int tile = mid_tile(pl.pr), blk = mid_block(pl.pr, tile);                              \
         if (tile == 8 && blk == 1024)                                                                \
-            KERNEL<8, 1024><<<pl.pr.C / 8, 1024, 0, stream>>>(__VA_ARGS__);                          \
+            KERNEL<float, 8, 1024><<<pl.pr.C / 8, 1024, 0, stream>>>(__VA_ARGS__);                   \
         else if (tile == 8)                                                                          \
-            KERNEL<8, kBlock><<<pl.pr.C / 8, kBlock, 0, stream>>>(__VA_ARGS__);                      \
+            KERNEL<float, 8, kBlock><<<pl.pr.C / 8, kBlock, 0, stream>>>(__VA_ARGS__);               \
         else if (tile == 4 && blk == 1024)                                                           \
-            KERNEL<4, 1024><<<pl.pr.C / 4, 1024, 0, stream>>>(__VA_ARGS__);                          \
+            KERNEL<float, 4, 1024><<<pl.pr.C / 4, 1024, 0, stream>>>(__VA_ARGS__);                   \
         else if (tile == 4)                                                                          \
-            KERNEL<4, kBlock><<<pl.pr.C / 4, kBlock, 0, stream>>>(__VA_ARGS__);                      \
+            KERNEL<float, 4, kBlock><<<pl.pr.C / 4, kBlock, 0, stream>>>(__VA_ARGS__);               \
         else if (blk == 1024)                                                                        \
-            KERNEL<1, 1024><<<pl.pr.C, 1024, 0, stream>>>(__VA_ARGS__);                              \
+            KERNEL<float, 1, 1024><<<pl.pr.C, 1024, 0, stream>>>(__VA_ARGS__);                       \
         else                                                                                         \
-            KERNEL<1, kBlock><<<pl.pr.C, kBlock, 0, stream>>>(__VA_ARGS__);                          \
+            KERNEL<float, 1, kBlock><<<pl.pr.C, kBlock, 0, stream>>>(__VA_ARGS__);                   \
     } while (0)
 
 void launch_mid_fwd(const Plan& pl, const double* mom, const int64_t* perm, const int64_t* chan_perm, GateDev g,
@@ -73,7 +73,7 @@ void launch_mid_bwd(const Plan& pl, const float* sums, const double* saved, cons
                     float* coef, hipStream_t stream) {
     CNSN_MID_DISPATCH(mid_bwd_a_kernel, pl.mid, sums, saved, perm, chan_perm, g, f, dg, df, tmp, coef);
     if (pl.mid.cn_active)  // (without CrossNorm mid_bwd_a has written the coefficients itself)
-        mid_bwd_b_kernel<<<(int)((pl.P + kBlock - 1) / kBlock), kBlock, 0, stream>>>(pl.mid, saved, tmp, coef);
+        mid_bwd_b_kernel<float><<<(int)((pl.P + kBlock - 1) / kBlock), kBlock, 0, stream>>>(pl.mid, saved, tmp, coef);
 }
 #undef CNSN_MID_DISPATCH
 
@@ -389,23 +389,18 @@ int cnsn_plane_stats(const void* x, int dtype, int N, int C, int H, int W, const
                      float* mean_std, void* stream_) {
     int st = check_tensor(x, dtype, N, C, H, W);
     if (st) return st;
-    if (!mean_std) return CNSN_E_NULL;
-    float* mean = mean_std;  // the kernel writes row 0 (mean) and row 1 (std) of the (2, N*C) block
-    Box cb;
-    bool boxed;
-    st = parse_box(box, H, W, cb, boxed);
+    if (!mean_std) return CNSN_E_NULL;  // (the kernel writes row 0 (mean) and row 1 (std) of the (2, N*C) block)
+    PlaneCall pc;
+    st = plane_call(dtype, N, C, H, W, box, pc);
     if (st) return st;
-    const Shape s = pick_shape(dtype, H * W, W, boxed);
-    const Geom g = make_geom(N, C, H, W, s.vec, cb, cb);
-    const int blocks = blocks_for(g.P, s.lpp);
     hipStream_t stream = (hipStream_t)stream_;
-    dispatch(dtype, s, [&](auto tt, auto vt, auto lt) {
+    dispatch(dtype, pc.s, [&](auto tt, auto vt, auto lt) {
         using T = typename decltype(tt)::type;
         constexpr int VEC = decltype(vt)::value, LPP = decltype(lt)::value;
-        if (boxed)
-            plane_stats_kernel<T, VEC, LPP, true><<<blocks, kBlock, 0, stream>>>((const T*)x, g, nullptr, mean, eps);
+        if (pc.boxed)
+            plane_stats_kernel<T, VEC, LPP, true><<<pc.blocks, kBlock, 0, stream>>>((const T*)x, pc.g, nullptr, mean_std, eps);
         else
-            plane_stats_kernel<T, VEC, LPP, false><<<blocks, kBlock, 0, stream>>>((const T*)x, g, nullptr, mean, eps);
+            plane_stats_kernel<T, VEC, LPP, false><<<pc.blocks, kBlock, 0, stream>>>((const T*)x, pc.g, nullptr, mean_std, eps);
     });
     return launch_status();
 }
@@ -417,23 +412,19 @@ int cnsn_plane_stats_backward(const void* x, int dtype, int N, int C, int H, int
     if (st) return st;
     if (!mean || !std || !dmean || !dstd || !dx) return CNSN_E_NULL;
     if (((uintptr_t)dx & 15u) != 0) return CNSN_E_ALIGN;
-    Box cb;
-    bool boxed;
-    st = parse_box(box, H, W, cb, boxed);
+    PlaneCall pc;
+    st = plane_call(dtype, N, C, H, W, box, pc);
     if (st) return st;
-    const Shape s = pick_shape(dtype, H * W, W, boxed);
-    const Geom g = make_geom(N, C, H, W, s.vec, cb, cb);
-    const int blocks = blocks_for(g.P, s.lpp);
     hipStream_t stream = (hipStream_t)stream_;
-    dispatch(dtype, s, [&](auto tt, auto vt, auto lt) {
+    dispatch(dtype, pc.s, [&](auto tt, auto vt, auto lt) {
         using T = typename decltype(tt)::type;
         constexpr int VEC = decltype(vt)::value, LPP = decltype(lt)::value;
-        if (boxed)
-            plane_stats_bwd_kernel<T, VEC, LPP, true><<<blocks, kBlock, 0, stream>>>((const T*)x, (T*)dx, g, mean, std,
-                                                                                    dmean, dstd);
+        if (pc.boxed)
+            plane_stats_bwd_kernel<T, VEC, LPP, true><<<pc.blocks, kBlock, 0, stream>>>((const T*)x, (T*)dx, pc.g, mean, std,
+                                                                                       dmean, dstd);
         else
-            plane_stats_bwd_kernel<T, VEC, LPP, false><<<blocks, kBlock, 0, stream>>>((const T*)x, (T*)dx, g, mean,
-                                                                                     std, dmean, dstd);
+            plane_stats_bwd_kernel<T, VEC, LPP, false><<<pc.blocks, kBlock, 0, stream>>>((const T*)x, (T*)dx, pc.g, mean, std,
+                                                                                        dmean, dstd);
     });
     return launch_status();
 }
@@ -444,16 +435,15 @@ int cnsn_plane_affine(const void* x, int dtype, int N, int C, int H, int W, cons
     if (st) return st;
     if (!scale || !shift || !y) return CNSN_E_NULL;
     if (((uintptr_t)y & 15u) != 0) return CNSN_E_ALIGN;
-    const Shape s = pick_shape(dtype, H * W, W, false);
-    const Box whole{0, 0, H, W};
-    const Geom g = make_geom(N, C, H, W, s.vec, whole, whole);
-    const int blocks = blocks_for(g.P, s.lpp);
+    PlaneCall pc;
+    st = plane_call(dtype, N, C, H, W, nullptr, pc);
+    if (st) return st;
     hipStream_t stream = (hipStream_t)stream_;
     ApplyCoef cf{scale, nullptr, shift, nullptr, nullptr};
-    dispatch(dtype, s, [&](auto tt, auto vt, auto lt) {
+    dispatch(dtype, pc.s, [&](auto tt, auto vt, auto lt) {
         using T = typename decltype(tt)::type;
         constexpr int VEC = decltype(vt)::value, LPP = decltype(lt)::value;
-        apply_fwd_kernel<T, VEC, LPP, false><<<blocks, kBlock, 0, stream>>>((const T*)x, (T*)y, g, cf);
+        apply_fwd_kernel<T, VEC, LPP, false><<<pc.blocks, kBlock, 0, stream>>>((const T*)x, (T*)y, pc.g, cf);
     });
     return launch_status();
 }
@@ -465,15 +455,14 @@ int cnsn_plane_dot(const void* gr, const void* x, int dtype, int N, int C, int H
     st = check_tensor(gr, dtype, N, C, H, W);
     if (st) return st;
     if (!sum_g) return CNSN_E_NULL;
-    const Shape s = pick_shape(dtype, H * W, W, false);
-    const Box whole{0, 0, H, W};
-    const Geom g = make_geom(N, C, H, W, s.vec, whole, whole);
-    const int blocks = blocks_for(g.P, s.lpp);
+    PlaneCall pc;
+    st = plane_call(dtype, N, C, H, W, nullptr, pc);
+    if (st) return st;
     hipStream_t stream = (hipStream_t)stream_;
-    dispatch(dtype, s, [&](auto tt, auto vt, auto lt) {
+    dispatch(dtype, pc.s, [&](auto tt, auto vt, auto lt) {
         using T = typename decltype(tt)::type;
         constexpr int VEC = decltype(vt)::value, LPP = decltype(lt)::value;
-        bwd_reduce_kernel<T, VEC, LPP, false><<<blocks, kBlock, 0, stream>>>((const T*)gr, (const T*)x, g, nullptr,
+        bwd_reduce_kernel<T, VEC, LPP, false><<<pc.blocks, kBlock, 0, stream>>>((const T*)gr, (const T*)x, pc.g, nullptr,
                                                                             nullptr, 0, sum_g);
     });
     return launch_status();
@@ -486,15 +475,14 @@ int cnsn_plane_dot_shifted(const void* gr, const void* x, int dtype, int N, int 
     st = check_tensor(gr, dtype, N, C, H, W);
     if (st) return st;
     if (!sum_g || !shift) return CNSN_E_NULL;
-    const Shape s = pick_shape(dtype, H * W, W, false);
-    const Box whole{0, 0, H, W};
-    const Geom g = make_geom(N, C, H, W, s.vec, whole, whole);
-    const int blocks = blocks_for(g.P, s.lpp);
+    PlaneCall pc;
+    st = plane_call(dtype, N, C, H, W, nullptr, pc);
+    if (st) return st;
     hipStream_t stream = (hipStream_t)stream_;
-    dispatch(dtype, s, [&](auto tt, auto vt, auto lt) {
+    dispatch(dtype, pc.s, [&](auto tt, auto vt, auto lt) {
         using T = typename decltype(tt)::type;
         constexpr int VEC = decltype(vt)::value, LPP = decltype(lt)::value;
-        bwd_reduce_kernel<T, VEC, LPP, false><<<blocks, kBlock, 0, stream>>>((const T*)gr, (const T*)x, g, shift, nullptr, 1,
+        bwd_reduce_kernel<T, VEC, LPP, false><<<pc.blocks, kBlock, 0, stream>>>((const T*)gr, (const T*)x, pc.g, shift, nullptr, 1,
                                                                             sum_g);
     });
     return launch_status();
@@ -508,15 +496,14 @@ int cnsn_plane_combine(const void* gr, const void* x, int dtype, int N, int C, i
     if (st) return st;
     if (!coef || !out) return CNSN_E_NULL;
     if (((uintptr_t)out & 15u) != 0) return CNSN_E_ALIGN;
-    const Shape s = pick_shape(dtype, H * W, W, false);
-    const Box whole{0, 0, H, W};
-    const Geom g = make_geom(N, C, H, W, s.vec, whole, whole);
-    const int blocks = blocks_for(g.P, s.lpp);
+    PlaneCall pc;
+    st = plane_call(dtype, N, C, H, W, nullptr, pc);
+    if (st) return st;
     hipStream_t stream = (hipStream_t)stream_;
-    dispatch(dtype, s, [&](auto tt, auto vt, auto lt) {
+    dispatch(dtype, pc.s, [&](auto tt, auto vt, auto lt) {
         using T = typename decltype(tt)::type;
         constexpr int VEC = decltype(vt)::value, LPP = decltype(lt)::value;
-        apply_bwd_kernel<T, VEC, LPP, false><<<blocks, kBlock, 0, stream>>>((const T*)gr, (const T*)x, (T*)out, g, coef);
+        apply_bwd_kernel<T, VEC, LPP, false><<<pc.blocks, kBlock, 0, stream>>>((const T*)gr, (const T*)x, (T*)out, pc.g, coef);
     });
     return launch_status();
 }

@@ -9,40 +9,48 @@
 #pragma once
 #include "cnsn_device.h"
 
-// A: the launch's scalar block: MidArgs, or the float64 path's MidArgsD (the same fields with double scalars,
-// cnsn_f64_kernels.h).  S (fwd_coefs, bwd_coefs): the type the apply coefficients are stored in.
+// A: the launch's scalar block: MidArgs, or MidArgsT<double> of a float64 call (the same fields with double scalars).
+// S (fwd_coefs, bwd_coefs, fix_sums): the type the apply coefficients and the per-plane sums are stored in, acc_t of the
+// tensor's element type (cnsn_device.h).
 #define CNSN_ALGEBRA_FN template <typename R, typename A = MidArgs> __device__ __forceinline__
 
 namespace cnsn {
 
-struct MidArgs {
+// S: float, or double for a float64 call (float(0.3) is 1e-8 away from 0.3)
+template <typename S>
+struct MidArgsT {
     int N, C, M;
     int Mc, Ms;  // content / style region sizes (M without a box)
     int cn_active, boxed, sn_active, sn_two, sn_training;
-    float lam, eps_cn, eps_sn, eps_bn, momentum;
+    S lam, eps_cn, eps_sn, eps_bn, momentum;
     double inv_n;     // 1/N         (host-computed: no fp64 divisions on the device)
     double unbias_n;  // N/(N-1)     (running_var takes the unbiased batch variance)
-    int save_coefs;   // forward: also keep the five apply coefficients in `saved` (ReLU-fused backward)
+    int save_coefs;   // forward: also keep the five apply coefficients in `saved` (ReLU-fused backward; float calls only)
 };
+using MidArgs = MidArgsT<float>;
 
-struct GateDev {
-    const float* w;      // (C,2)  Conv1d(C,C,k=2,groups=C) weight (cnsn.py:119)
-    const float* gamma;  // (C)    BatchNorm1d weight
-    const float* beta;   // (C)    BatchNorm1d bias
-    float* run_mean;     // (C)
-    float* run_var;      // (C)
-    long long* nbt;      // BatchNorm1d.num_batches_tracked (int64 scalar) or null: the forward adds 1 in training mode
+template <typename S>
+struct GateDevT {
+    const S* w;      // (C,2)  Conv1d(C,C,k=2,groups=C) weight (cnsn.py:119)
+    const S* gamma;  // (C)    BatchNorm1d weight
+    const S* beta;   // (C)    BatchNorm1d bias
+    S* run_mean;     // (C)
+    S* run_var;      // (C)
+    long long* nbt;  // BatchNorm1d.num_batches_tracked (int64 scalar) or null: the forward adds 1 in training mode
 };
+using GateDev = GateDevT<float>;
 // nn.BatchNorm1d.forward's `self.num_batches_tracked.add_(1)` (models/cnsn.py:121,138 call the module): done by the ONE thread
 // of the launch that updates channel 0's running statistics
 __device__ __forceinline__ void bump_batches_tracked(long long* nbt) {
     if (nbt) *nbt += 1;
 }
-struct GateGradDev {
-    float* dw;
-    float* dgamma;
-    float* dbeta;
+template <typename S>
+struct GateGradDevT {
+    S* dw;
+    S* dgamma;
+    S* dbeta;
 };
+using GateGradDev = GateGradDevT<float>;
 
 // region moments of one plane as pass A produces them
 template <typename R>
@@ -136,14 +144,14 @@ struct BwdSumsT {
 };
 using BwdSums = BwdSumsT<double>;
 
-// pass A' shifts x by float(mu): sum G*(x-mu) = S2 + (float(mu)-mu)*S1
-CNSN_ALGEBRA_FN BwdSumsT<R> fix_sums(const MidArgs& a, float s1i, float s2i, float s1o, float s2o, double mu_c,
-                               double mu_o) {
+// pass A' shifts x by S(mu): sum G*(x-mu) = S2 + (S(mu)-mu)*S1 (S = double: the correction is exactly zero)
+template <typename R, typename S = float, typename A = MidArgs>
+__device__ __forceinline__ BwdSumsT<R> fix_sums(const A& a, S s1i, S s2i, S s1o, S s2o, double mu_c, double mu_o) {
     BwdSumsT<R> s;
     s.S1in = s1i;
-    s.S2in = (R)((double)s2i + ((double)(float)mu_c - mu_c) * (double)s1i);
+    s.S2in = (R)((double)s2i + ((double)(S)mu_c - mu_c) * (double)s1i);
     s.S1out = a.boxed ? (R)s1o : R(0);
-    s.S2out = a.boxed ? (R)((double)s2o + ((double)(float)mu_o - mu_o) * (double)s1o) : R(0);
+    s.S2out = a.boxed ? (R)((double)s2o + ((double)(S)mu_o - mu_o) * (double)s1o) : R(0);
     return s;
 }
 

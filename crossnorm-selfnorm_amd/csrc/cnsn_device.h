@@ -8,11 +8,24 @@ namespace cnsn {
 constexpr int kBlock = 256;  // 4 waves of 64 lanes
 
 // ------------------------------------------------------------------------------------------------
-// element types: float, bf16 (own bit-level type), _Float16
+// element types: float, bf16 (own bit-level type), _Float16, double
 // ------------------------------------------------------------------------------------------------
 struct bf16_t {
     uint16_t bits;
 };
+
+// the type a tensor of T is computed in: accumulators, per-plane coefficients, gate parameters, running statistics and parameter
+// gradients.  float for the 16- and 32-bit element types; double tensors are double from the element to the result
+template <typename T>
+struct AccOf {
+    using type = float;
+};
+template <>
+struct AccOf<double> {
+    using type = double;
+};
+template <typename T>
+using acc_t = typename AccOf<T>::type;
 
 __device__ __forceinline__ float to_float(float v) { return v; }
 __device__ __forceinline__ float to_float(bf16_t v) { return __uint_as_float(uint32_t(v.bits) << 16); }
@@ -34,6 +47,23 @@ __device__ __forceinline__ bf16_t from_float<bf16_t>(float f) {
 template <>
 __device__ __forceinline__ _Float16 from_float<_Float16>(float f) {
     return _Float16(f);
+}
+
+template <typename T>
+__device__ __forceinline__ acc_t<T> to_acc(T v) {
+    return to_float(v);
+}
+template <>
+__device__ __forceinline__ double to_acc<double>(double v) {
+    return v;
+}
+template <typename T>
+__device__ __forceinline__ T from_acc(acc_t<T> a) {
+    return from_float<T>(a);
+}
+template <>
+__device__ __forceinline__ double from_acc<double>(double a) {
+    return a;
 }
 
 // VEC consecutive elements moved by ONE global_load / global_store of VEC*sizeof(T) bytes
@@ -150,6 +180,32 @@ __device__ __forceinline__ void group_sum(float (&acc)[NACC], float* lds) {
     }
 }
 
+// the same for doubles (no DPP for 64-bit values: an xor butterfly).  Every lane of a group adds in the same order: the sums do
+// not depend on the grid
+template <int LPP, int NACC>
+__device__ __forceinline__ void group_sum(double (&acc)[NACC], double* lds) {
+    static_assert(LPP == 16 || LPP == 64 || LPP == 256, "lanes per plane must be 16, 64 or 256");
+    constexpr int W = LPP < 64 ? LPP : 64;
+#pragma unroll
+    for (int k = 0; k < NACC; ++k) {
+        double v = acc[k];
+#pragma unroll
+        for (int o = W / 2; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
+        acc[k] = v;
+    }
+    if constexpr (LPP == 256) {
+        const int wave = threadIdx.x >> 6;
+        __syncthreads();
+        if ((threadIdx.x & 63) == 0) {
+#pragma unroll
+            for (int k = 0; k < NACC; ++k) lds[wave * NACC + k] = acc[k];
+        }
+        __syncthreads();
+#pragma unroll
+        for (int k = 0; k < NACC; ++k) acc[k] = (lds[k] + lds[NACC + k]) + (lds[2 * NACC + k] + lds[3 * NACC + k]);
+    }
+}
+
 // block-wide sum of NACC doubles through LDS (mid kernels; one block per channel)
 template <int NACC>
 __device__ __forceinline__ void block_sum_d(double (&acc)[NACC], double* lds) {
@@ -230,5 +286,6 @@ __host__ __device__ inline int shift_sample_pixel(int H, int W, int i) {
     return shift_sample_coord(H, i) * W + shift_sample_coord(W, i);
 }
 __device__ __forceinline__ float median3(float a, float b, float c) { return fmaxf(fminf(a, b), fminf(fmaxf(a, b), c)); }
+__device__ __forceinline__ double median3(double a, double b, double c) { return fmax(fmin(a, b), fmin(fmax(a, b), c)); }
 
 }  // namespace cnsn

@@ -10,7 +10,7 @@
 
 namespace cnsn {
 
-inline int elem_bytes(int dtype) { return dtype == CNSN_F32 ? 4 : 2; }
+inline int elem_bytes(int dtype) { return dtype == CNSN_F64 ? 8 : (dtype == CNSN_F32 ? 4 : 2); }
 
 // widest power-of-two vector (<= 16 B) that divides `span` elements
 inline int pick_vec(int dtype, int span) {

@@ -1,7 +1,13 @@
 // "Mid" kernels of the two-pass strategy: everything the fused op does on N*C scalars between two
 // tensor passes.  One workgroup per channel (SelfNorm's BatchNorm1d couples the N planes of a
 // channel, models/cnsn.py:121,138); the per-plane algebra lives in cnsn_algebra.h.
+//
+// S: the type of everything outside `saved`, the moments and the scratch rows (those are double in any case): sums in,
+// coefficients out, gate parameters, running statistics, parameter gradients and the launch's scalars.  float for float, bf16
+// and f16 tensors; double for double tensors (acc_t, cnsn_device.h), where nothing around the R = double algebra is rounded.
 #pragma once
+#include <type_traits>
+
 #include "cnsn_algebra.h"
 #include "cnsn_device.h"
 #include "cnsn_layout.h"
@@ -45,11 +51,11 @@ __device__ __forceinline__ void tile_sum_d(double (&acc)[NACC], double* lds) {
     }
 }
 
-template <int TC, int BLK>
-__global__ __launch_bounds__(BLK) void mid_fwd_kernel(MidArgs a, const double* __restrict__ mom,
+template <typename S, int TC, int BLK>
+__global__ __launch_bounds__(BLK) void mid_fwd_kernel(MidArgsT<S> a, const double* __restrict__ mom,
                                                          const int64_t* __restrict__ perm,
-                                                         const int64_t* __restrict__ chan_perm, GateDev gg, GateDev gf,
-                                                         float* __restrict__ coef, double* __restrict__ saved) {
+                                                         const int64_t* __restrict__ chan_perm, GateDevT<S> gg, GateDevT<S> gf,
+                                                         S* __restrict__ coef, double* __restrict__ saved) {
     __shared__ double red[(BLK / 64) * 2 * TC];
     constexpr int NSTEP = BLK / TC;                    // instances per sweep step
     const int n0 = threadIdx.x / TC;                   // first instance of this thread
@@ -57,6 +63,15 @@ __global__ __launch_bounds__(BLK) void mid_fwd_kernel(MidArgs a, const double* _
     const int c = blockIdx.x * TC + threadIdx.x % TC;  // (C is a multiple of TC)
     const size_t P = (size_t)a.N * a.C;
     const int cs = (a.cn_active && chan_perm) ? (int)chan_perm[c] : c;
+    // nn.BatchNorm1d.forward's num_batches_tracked.add_(1): ONE thread of the launch, next to channel 0's running statistics
+    // below.  S = double does it here instead: with the two counters' addresses live across the sweeps that instantiation keeps
+    // a 68-byte stack frame (profiles/r11_f64.md, section 3) — the one place where the two types differ in statement order
+    if constexpr (std::is_same_v<S, double>) {
+        if (a.sn_active && a.sn_training && lead && c == 0) {
+            bump_batches_tracked(gg.nbt);
+            if (a.sn_two) bump_batches_tracked(gf.nbt);
+        }
+    }
 
     double wg0 = 0, wg1 = 0, wf0 = 0, wf1 = 0;
     if (a.sn_active) {
@@ -120,15 +135,17 @@ __global__ __launch_bounds__(BLK) void mid_fwd_kernel(MidArgs a, const double* _
             rf = 1.0 / sqrt(vf + (double)a.eps_bn);
             if (lead) {
                 const double mom_ = a.momentum, unb = (double)a.N / ((double)a.N - 1.0);
-                gg.run_mean[c] = (float)((1.0 - mom_) * gg.run_mean[c] + mom_ * mg);
-                gg.run_var[c] = (float)((1.0 - mom_) * gg.run_var[c] + mom_ * vg * unb);
+                gg.run_mean[c] = (S)((1.0 - mom_) * gg.run_mean[c] + mom_ * mg);
+                gg.run_var[c] = (S)((1.0 - mom_) * gg.run_var[c] + mom_ * vg * unb);
                 if (a.sn_two) {
-                    gf.run_mean[c] = (float)((1.0 - mom_) * gf.run_mean[c] + mom_ * mf);
-                    gf.run_var[c] = (float)((1.0 - mom_) * gf.run_var[c] + mom_ * vf * unb);
+                    gf.run_mean[c] = (S)((1.0 - mom_) * gf.run_mean[c] + mom_ * mf);
+                    gf.run_var[c] = (S)((1.0 - mom_) * gf.run_var[c] + mom_ * vf * unb);
                 }
-                if (c == 0) {
-                    bump_batches_tracked(gg.nbt);
-                    if (a.sn_two) bump_batches_tracked(gf.nbt);
+                if constexpr (!std::is_same_v<S, double>) {
+                    if (c == 0) {
+                        bump_batches_tracked(gg.nbt);
+                        if (a.sn_two) bump_batches_tracked(gf.nbt);
+                    }
                 }
             }
         } else {
@@ -170,25 +187,27 @@ __global__ __launch_bounds__(BLK) void mid_fwd_kernel(MidArgs a, const double* _
         fp.a1 = cr.a1;
         fp.m_in = cr.m_in;
         fp.mu_p = saved[sv_at(ps, SV_MU_P)];
-        const FwdCoefs k = fwd_coefs<double>(a, fp, g, f);
+        const FwdCoefsT<S> k = fwd_coefs<double, S>(a, fp, g, f);
         coef[FC_A_IN * P + p] = k.a_in;
         coef[FC_XR * P + p] = k.xr;
         coef[FC_B_IN * P + p] = k.b_in;
         coef[FC_A_OUT * P + p] = k.a_out;
         coef[FC_B_OUT * P + p] = k.b_out;
-        if (a.save_coefs) store_fwd_coefs(saved, ps, k);
+        if constexpr (std::is_same_v<S, float>) {  // (a float64 call has no fused epilogue)
+            if (a.save_coefs) store_fwd_coefs(saved, ps, k);
+        }
     }
 }
 
 // per channel: gate / BatchNorm backward, parameter gradients, statistic gradients per plane;
 // scatters the style-statistic gradients to the planes that lent their statistics.
-template <int TC, int BLK>
-__global__ __launch_bounds__(BLK) void mid_bwd_a_kernel(MidArgs a, const float* __restrict__ sums,
+template <typename S, int TC, int BLK>
+__global__ __launch_bounds__(BLK) void mid_bwd_a_kernel(MidArgsT<S> a, const S* __restrict__ sums,
                                                            const double* __restrict__ saved,
                                                            const int64_t* __restrict__ perm,
-                                                           const int64_t* __restrict__ chan_perm, GateDev gg, GateDev gf,
-                                                           GateGradDev dg, GateGradDev df, double* __restrict__ tmp,
-                                                           float* __restrict__ coef) {
+                                                           const int64_t* __restrict__ chan_perm, GateDevT<S> gg, GateDevT<S> gf,
+                                                           GateGradDevT<S> dg, GateGradDevT<S> df, double* __restrict__ tmp,
+                                                           S* __restrict__ coef) {
     __shared__ double red[(BLK / 64) * 4 * TC];
     constexpr int NSTEP = BLK / TC;
     const int n0 = threadIdx.x / TC;
@@ -198,8 +217,8 @@ __global__ __launch_bounds__(BLK) void mid_bwd_a_kernel(MidArgs a, const float* 
     const int cs = (a.cn_active && chan_perm) ? (int)chan_perm[c] : c;
 
     auto sums_of = [&](size_t p, SvRec ps) {
-        return fix_sums<double>(a, sums[p], sums[P + p], a.boxed ? sums[2 * P + p] : 0.f, a.boxed ? sums[3 * P + p] : 0.f,
-                        saved[sv_at(ps, SV_MU_C)], a.boxed ? saved[sv_at(ps, SV_MU_O)] : 0.0);
+        return fix_sums<double, S>(a, sums[p], sums[P + p], a.boxed ? sums[2 * P + p] : S(0), a.boxed ? sums[3 * P + p] : S(0),
+                                   saved[sv_at(ps, SV_MU_C)], a.boxed ? saved[sv_at(ps, SV_MU_O)] : 0.0);
     };
 
     // ---- sweep 1: dL/dgate -> through the sigmoid; batch sums for BatchNorm backward
@@ -221,11 +240,11 @@ __global__ __launch_bounds__(BLK) void mid_bwd_a_kernel(MidArgs a, const float* 
         }
         tile_sum_d<4, TC, BLK>(s, red);
         if (lead) {
-            dg.dgamma[c] = (float)s[1];
-            dg.dbeta[c] = (float)s[0];
+            dg.dgamma[c] = (S)s[1];
+            dg.dbeta[c] = (S)s[0];
             if (a.sn_two) {
-                df.dgamma[c] = (float)s[3];
-                df.dbeta[c] = (float)s[2];
+                df.dgamma[c] = (S)s[3];
+                df.dbeta[c] = (S)s[2];
             }
         }
     }
@@ -263,8 +282,8 @@ __global__ __launch_bounds__(BLK) void mid_bwd_a_kernel(MidArgs a, const float* 
         if (!a.cn_active) {
             // no plane lends statistics to another one: the coefficients of dx are complete here, mid_bwd_b_kernel is not launched
             // (launch_mid_bwd) and the two scratch rows it would read are not written
-            const BwdCoefs k = bwd_coefs<double>(a, o, 0.0, 0.0, saved[sv_at(ps, SV_G)], cr.a1, cr.m_in, mu_p, saved[sv_at(ps, SV_MU_C)],
-                                                 cr.sig_c, cr.mu_s, cr.sig_s);
+            const BwdCoefsT<S> k = bwd_coefs<double, S>(a, o, 0.0, 0.0, saved[sv_at(ps, SV_G)], cr.a1, cr.m_in, mu_p,
+                                                        saved[sv_at(ps, SV_MU_C)], cr.sig_c, cr.mu_s, cr.sig_s);
             coef[BC_CG_IN * P + p] = k.cG_in;
             coef[BC_CX_IN * P + p] = k.cX_in;
             coef[BC_XR_IN * P + p] = k.xr_in;
@@ -293,19 +312,20 @@ __global__ __launch_bounds__(BLK) void mid_bwd_a_kernel(MidArgs a, const float* 
     if (a.sn_active) {
         tile_sum_d<4, TC, BLK>(sw, red);
         if (lead) {
-            dg.dw[2 * c] = (float)sw[0];
-            dg.dw[2 * c + 1] = (float)sw[1];
+            dg.dw[2 * c] = (S)sw[0];
+            dg.dw[2 * c + 1] = (S)sw[1];
             if (a.sn_two) {
-                df.dw[2 * c] = (float)sw[2];
-                df.dw[2 * c + 1] = (float)sw[3];
+                df.dw[2 * c] = (S)sw[2];
+                df.dw[2 * c + 1] = (S)sw[3];
             }
         }
     }
 }
 
 // per plane: assemble the coefficients of dx = cG*G + cX*(x-xr) + c0 (+ style term)
-__global__ __launch_bounds__(kBlock) void mid_bwd_b_kernel(MidArgs a, const double* __restrict__ saved,
-                                                           const double* __restrict__ tmp, float* __restrict__ coef) {
+template <typename S>
+__global__ __launch_bounds__(kBlock) void mid_bwd_b_kernel(MidArgsT<S> a, const double* __restrict__ saved,
+                                                           const double* __restrict__ tmp, S* __restrict__ coef) {
     const size_t P = (size_t)a.N * a.C;
     const size_t p = (size_t)blockIdx.x * kBlock + threadIdx.x;
     const SvRec ps = sv_rec_of_plane(p, a.N, a.C);
@@ -321,8 +341,8 @@ __global__ __launch_bounds__(kBlock) void mid_bwd_b_kernel(MidArgs a, const doub
         Esig = tmp[BT_E_SIG * P + p];
     }
     const CnRowsT<double> cr = load_cn_rows<double>(a, saved, ps, saved[sv_at(ps, SV_MU_C)]);
-    const BwdCoefs k = bwd_coefs<double>(a, o, Emu, Esig, saved[sv_at(ps, SV_G)], cr.a1, cr.m_in, saved[sv_at(ps, SV_MU_P)],
-                                         saved[sv_at(ps, SV_MU_C)], cr.sig_c, cr.mu_s, cr.sig_s);
+    const BwdCoefsT<S> k = bwd_coefs<double, S>(a, o, Emu, Esig, saved[sv_at(ps, SV_G)], cr.a1, cr.m_in, saved[sv_at(ps, SV_MU_P)],
+                                                saved[sv_at(ps, SV_MU_C)], cr.sig_c, cr.mu_s, cr.sig_s);
     coef[BC_CG_IN * P + p] = k.cG_in;
     coef[BC_CX_IN * P + p] = k.cX_in;
     coef[BC_XR_IN * P + p] = k.xr_in;

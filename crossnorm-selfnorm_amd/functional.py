@@ -48,15 +48,16 @@ def resident_allowed() -> bool:
     return _resident_set if _resident_set is not None else os.environ.get("CNSN_RESIDENT", "1") != "0"
 
 
-def _require_device(x: torch.Tensor, what: str):
+def _require_device(x: torch.Tensor, what: str, dtypes=_DTYPES):
+    """`dtypes`: the element types the entry point takes (the float64 entry points: float64 alone)"""
     if not isinstance(x, torch.Tensor):
         raise TypeError(f"{what}: expected a tensor")
     if not x.is_cuda:
         raise _ffi.CnsnError(
             f"{what}: got a {x.device.type} tensor. This implementation runs on MI355X HIP device "
             "tensors only; there is no CPU path.")
-    if x.dtype not in _DTYPES:
-        raise TypeError(f"{what}: dtype {x.dtype} not supported (float32, bfloat16, float16)")
+    if x.dtype not in dtypes:
+        raise TypeError(f"{what}: dtype {x.dtype} not supported ({', '.join(str(d)[6:] for d in dtypes)})")
     assert x.dim() == 4, "expected an (N, C, H, W) tensor"          # reference cnsn.py:12
 
 
@@ -125,10 +126,15 @@ def _ptr(t: Optional[torch.Tensor]):
     return C.c_void_p(t.data_ptr()) if t is not None else None
 
 
-def _f32(t: torch.Tensor) -> torch.Tensor:
-    if t.dtype == torch.float32 and t.is_contiguous():
+def _as(t: torch.Tensor, dtype) -> torch.Tensor:
+    """`t` as the kernels take a side array: contiguous, of `dtype`, detached"""
+    if t.dtype == dtype and t.is_contiguous():
         return t.detach() if t.requires_grad else t
-    return t.detach().to(torch.float32).contiguous()
+    return t.detach().to(dtype).contiguous()
+
+
+def _f32(t: torch.Tensor) -> torch.Tensor:
+    return _as(t, torch.float32)
 
 
 # ---- the skeleton the autograd classes below share
@@ -160,12 +166,17 @@ def _cast_grads(tensors, dtypes):
     return [None if d is None else (t if t.dtype == d else t.to(d)) for t, d in zip(tensors, dtypes)]
 
 
-def _gate_grad_views(c: int, dev, extra: int = 0):
+def _abi_struct(struct, *fields):
+    """a struct of the ABI; the float64 ones lead with their own size and a reserved word"""
+    return struct(C.sizeof(struct), 0, *fields) if struct._fields_[0][0] == "struct_bytes" else struct(*fields)
+
+
+def _gate_grad_views(c: int, dev, extra: int = 0, dtype=torch.float32, struct=_ffi.GateGrad):
     """one allocation for a gate's gradients — d_fc_weight (C,1,2), d_bn_weight (C), d_bn_bias (C) — and `extra` more rows of C
-    floats behind them: (the views, the cnsn_gate_grad_t that points at the first three)"""
-    flat = torch.empty((4 + extra) * c, dtype=torch.float32, device=dev)
+    behind them: (the views, the cnsn_gate_grad_t / cnsn_gate_grad_f64_t that points at the first three)"""
+    flat = torch.empty((4 + extra) * c, dtype=dtype, device=dev)
     rows = [flat[:2 * c].view(c, 1, 2), *flat[2 * c:].view(2 + extra, c).unbind(0)]
-    return rows, _ffi.GateGrad(_ptr(rows[0]), _ptr(rows[1]), _ptr(rows[2]))
+    return rows, _abi_struct(struct, _ptr(rows[0]), _ptr(rows[1]), _ptr(rows[2]))
 
 
 def _plan_cache() -> dict:
@@ -388,35 +399,41 @@ def sn_cluster(x: torch.Tensor, cfg: FusedConfig, backward: bool = False) -> boo
     return st == 1
 
 
-def _problem(x: torch.Tensor, cfg: FusedConfig) -> _ffi.Problem:
+def _problem_shape(x: torch.Tensor, cfg: FusedConfig, dtype: int) -> _ffi.Problem:
+    """the part of cnsn_problem_t every call fills alike: element type, shape, boxes and mode flags"""
     p = _ffi.Problem()
     p.struct_bytes = C.sizeof(_ffi.Problem)
-    p.dtype = _DTYPES[x.dtype]
+    p.dtype = dtype
     p.N, p.C, p.H, p.W = (int(s) for s in x.shape)
     p.cn_active = int(cfg.cn_active)
     p.content_box = _ffi.box4(cfg.content_box)
     p.style_box = _ffi.box4(cfg.style_box)
-    p.lam = 0.0 if cfg.lam is None else float(cfg.lam)
-    p.eps_cn = cfg.eps_cn
     p.sn_active = int(cfg.sn_active)
     p.sn_two = int(cfg.sn_two)
     p.sn_training = int(cfg.sn_training)
+    return p
+
+
+def _problem(x: torch.Tensor, cfg: FusedConfig) -> _ffi.Problem:
+    p = _problem_shape(x, cfg, _DTYPES[x.dtype])
+    p.lam = 0.0 if cfg.lam is None else float(cfg.lam)
+    p.eps_cn = cfg.eps_cn
     p.eps_sn, p.eps_bn, p.momentum = cfg.eps_sn, cfg.eps_bn, cfg.momentum
     p.strategy = _strategy
     return p
 
 
 class _RunningBuffers:
-    """a BatchNorm's running statistics and counter as the kernels take them.  `direct`: the buffers themselves (contiguous
-    float32), else float32 copies that `write_back` copies into the module's after a training-mode launch.  `nbt`: the counter
+    """a BatchNorm's running statistics and counter as the kernels take them.  `direct`: the buffers themselves (contiguous,
+    of the kernels' `dtype`), else copies in that dtype that `write_back` copies into the module's after a training-mode launch.  `nbt`: the counter
     for the kernel to add 1 to — a counter it cannot reach (not ONE int64 on the device) is counted here, as
     nn.BatchNorm2d.forward does, and only in training mode; eval mode moves no counter and writes nothing back."""
 
-    def _take_running(self, rm, rv, nbt, training=True):
+    def _take_running(self, rm, rv, nbt, training=True, dtype=torch.float32):
         self.src_rm, self.src_rv, self.training = rm, rv, bool(training)
-        self.direct = rm.dtype == torch.float32 and rm.is_contiguous() and rv.dtype == torch.float32 and rv.is_contiguous()
-        self.rm = rm.detach() if self.direct else _f32(rm)
-        self.rv = rv.detach() if self.direct else _f32(rv)
+        self.direct = rm.dtype == dtype and rm.is_contiguous() and rv.dtype == dtype and rv.is_contiguous()
+        self.rm = rm.detach() if self.direct else _as(rm, dtype)
+        self.rv = rv.detach() if self.direct else _as(rv, dtype)
         if nbt is not None and not (training and nbt.dtype == torch.int64 and nbt.is_cuda and nbt.numel() == 1):
             if training:
                 nbt.add_(1)
@@ -430,12 +447,13 @@ class _RunningBuffers:
 
 
 class _GateBuffers(_RunningBuffers):
-    """float32 contiguous views/copies of a gate's tensors + the cnsn_gate_t that points at them."""
+    """contiguous views/copies of a gate's tensors in the kernels' `dtype` + the cnsn_gate_t (float64: cnsn_gate_f64_t) that
+    points at them.  A module of that dtype passes its parameters and buffers as they are."""
 
-    def __init__(self, w, gamma, beta, rm, rv, nbt=None):
-        self.w, self.gamma, self.beta = _f32(w), _f32(gamma), _f32(beta)
-        self._take_running(rm, rv, nbt)
-        self.c = _ffi.Gate(_ptr(self.w), _ptr(self.gamma), _ptr(self.beta), _ptr(self.rm), _ptr(self.rv), _ptr(self.nbt))
+    def __init__(self, w, gamma, beta, rm, rv, nbt=None, training=True, dtype=torch.float32, struct=_ffi.Gate):
+        self.w, self.gamma, self.beta = _as(w, dtype), _as(gamma, dtype), _as(beta, dtype)
+        self._take_running(rm, rv, nbt, training, dtype)
+        self.c = _abi_struct(struct, _ptr(self.w), _ptr(self.gamma), _ptr(self.beta), _ptr(self.rm), _ptr(self.rv), _ptr(self.nbt))
 
 
 class _Bn2dBuffers(_RunningBuffers):
@@ -845,41 +863,85 @@ def _dims(x):
     return tuple(int(s) for s in x.shape)
 
 
+def _plane_call(name, f64, tensors, x, *rest):
+    """one per-plane primitive on tensors shaped like `x`: cnsn_<name> (the dtype code follows the tensors) or cnsn_<name>_f64"""
+    fn = getattr(_ffi.lib(), f"cnsn_{name}_f64" if f64 else f"cnsn_{name}")
+    code = () if f64 else (_DTYPES[x.dtype],)
+    _ffi.check(fn(*(_ptr(t) for t in tensors), *code, *_dims(x), *rest, _stream(x)), fn.__name__)
+
+
+def _plane_dtypes(f64):
+    """(element types taken, dtype of the per-plane side arrays, allocator of an output) of the float / float64 primitives"""
+    return ((torch.float64,), torch.float64, torch.empty_like) if f64 else (_DTYPES, torch.float32, _out_like)
+
+
+def _plane_stats_forward(ctx, x, eps, box, f64):
+    dtypes, side, _ = _plane_dtypes(f64)
+    _require_device(x, "calc_ins_mean_std", dtypes)
+    x = _dense(x)
+    n, c = _dims(x)[:2]
+    ms = torch.empty(2, n * c, dtype=side, device=x.device)
+    _plane_call("plane_stats", f64, (x,), x, _ffi.box4(box) if box else None, float(eps), _ptr(ms))
+    ctx.box = box
+    ctx.save_for_backward(x, ms)
+    return ms[0].view(n, c, 1, 1), ms[1].view(n, c, 1, 1)
+
+
+def _plane_stats_backward(ctx, gmean, gstd, f64):
+    _, side, alloc = _plane_dtypes(f64)
+    x, ms = ctx.saved_tensors
+    gm, gs = _as(gmean, side).view(-1), _as(gstd, side).view(-1)
+    dx = alloc(x)
+    _plane_call("plane_stats_backward", f64, (x,), x, _ffi.box4(ctx.box) if ctx.box else None, _ptr(ms[0]), _ptr(ms[1]),
+                _ptr(gm), _ptr(gs), _ptr(dx))
+    return dx
+
+
+def _plane_affine_forward(ctx, x, scale, shift, f64):
+    dtypes, side, alloc = _plane_dtypes(f64)
+    _require_device(x, "plane_affine", dtypes)
+    x = _dense(x)
+    sc, sh = _as(scale, side).view(-1), _as(shift, side).view(-1)
+    assert sc.numel() == x.shape[0] * x.shape[1] and sh.numel() == sc.numel(), "one scale and one shift per plane"
+    y = alloc(x)
+    _plane_call("plane_affine", f64, (x,), x, _ptr(sc), _ptr(sh), _ptr(y))
+    ctx.save_for_backward(x, sc)
+    ctx.meta = (scale.shape, scale.dtype, shift.shape, shift.dtype)
+    return y
+
+
+def _plane_affine_backward(ctx, gy, f64):
+    _, side, alloc = _plane_dtypes(f64)
+    x, sc = ctx.saved_tensors
+    gy = _grad_like(gy, x, False)
+    dx = dscale = dshift = None
+    if ctx.needs_input_grad[0]:
+        dx = alloc(x)
+        zero = torch.zeros_like(sc)
+        _plane_call("plane_affine", f64, (gy,), x, _ptr(sc), _ptr(zero), _ptr(dx))
+    if ctx.needs_input_grad[1] or ctx.needs_input_grad[2]:
+        sums = torch.empty(2, sc.numel(), dtype=side, device=x.device)
+        _plane_call("plane_dot", f64, (gy, x), x, _ptr(sums))
+        s_shape, s_dtype, t_shape, t_dtype = ctx.meta
+        dscale = sums[1].view(s_shape).to(s_dtype)
+        dshift = sums[0].view(t_shape).to(t_dtype)
+    return dx, dscale, dshift
+
+
 class PlaneStats(torch.autograd.Function):
     """(mean, std) of every plane — cnsn_plane_stats / cnsn_plane_stats_backward."""
 
     @staticmethod
     @_on_device_of
     def forward(ctx, x, eps, box, keep_fp32=False):
-        _require_device(x, "calc_ins_mean_std")
-        lib = _ffi.lib()
-        x = _dense(x)
-        n, c, h, w = _dims(x)
-        ms = torch.empty(2, n * c, dtype=torch.float32, device=x.device)
-        st = lib.cnsn_plane_stats(_ptr(x), _DTYPES[x.dtype], n, c, h, w, _ffi.box4(box) if box else None,
-                                  float(eps), _ptr(ms), _stream(x))
-        _ffi.check(st, "cnsn_plane_stats")
-        ctx.box = box
-        ctx.save_for_backward(x, ms)
+        mean, std = _plane_stats_forward(ctx, x, eps, box, False)
         out_dtype = torch.float32 if keep_fp32 else x.dtype
-        mean = ms[0].view(n, c, 1, 1).to(out_dtype)
-        std = ms[1].view(n, c, 1, 1).to(out_dtype)
-        return mean, std
+        return mean.to(out_dtype), std.to(out_dtype)
 
     @staticmethod
     @_on_device_of
     def backward(ctx, gmean, gstd):
-        lib = _ffi.lib()
-        x, ms = ctx.saved_tensors
-        n, c, h, w = _dims(x)
-        gm = _f32(gmean).view(-1)
-        gs = _f32(gstd).view(-1)
-        dx = _out_like(x)
-        st = lib.cnsn_plane_stats_backward(_ptr(x), _DTYPES[x.dtype], n, c, h, w,
-                                           _ffi.box4(ctx.box) if ctx.box else None, _ptr(ms[0]), _ptr(ms[1]),
-                                           _ptr(gm), _ptr(gs), _ptr(dx), _stream(x))
-        _ffi.check(st, "cnsn_plane_stats_backward")
-        return dx, None, None, None
+        return _plane_stats_backward(ctx, gmean, gstd, False), None, None, None
 
 
 class PlaneAffine(torch.autograd.Function):
@@ -888,40 +950,12 @@ class PlaneAffine(torch.autograd.Function):
     @staticmethod
     @_on_device_of
     def forward(ctx, x, scale, shift):
-        _require_device(x, "plane_affine")
-        lib = _ffi.lib()
-        x = _dense(x)
-        n, c, h, w = _dims(x)
-        sc, sh = _f32(scale).view(-1), _f32(shift).view(-1)
-        y = _out_like(x)
-        st = lib.cnsn_plane_affine(_ptr(x), _DTYPES[x.dtype], n, c, h, w, _ptr(sc), _ptr(sh), _ptr(y), _stream(x))
-        _ffi.check(st, "cnsn_plane_affine")
-        ctx.save_for_backward(x, sc)
-        ctx.meta = (scale.shape, scale.dtype, shift.shape, shift.dtype)
-        return y
+        return _plane_affine_forward(ctx, x, scale, shift, False)
 
     @staticmethod
     @_on_device_of
     def backward(ctx, gy):
-        lib = _ffi.lib()
-        x, sc = ctx.saved_tensors
-        n, c, h, w = _dims(x)
-        gy = _dense(gy.to(x.dtype))
-        dt = _DTYPES[x.dtype]
-        dx = dscale = dshift = None
-        if ctx.needs_input_grad[0]:
-            dx = _out_like(x)
-            zero = torch.zeros_like(sc)
-            st = lib.cnsn_plane_affine(_ptr(gy), dt, n, c, h, w, _ptr(sc), _ptr(zero), _ptr(dx), _stream(x))
-            _ffi.check(st, "cnsn_plane_affine(backward)")
-        if ctx.needs_input_grad[1] or ctx.needs_input_grad[2]:
-            sums = torch.empty(2, n * c, dtype=torch.float32, device=x.device)
-            st = lib.cnsn_plane_dot(_ptr(gy), _ptr(x), dt, n, c, h, w, _ptr(sums), _stream(x))
-            _ffi.check(st, "cnsn_plane_dot")
-            s_shape, s_dtype, t_shape, t_dtype = ctx.meta
-            dscale = sums[1].view(s_shape).to(s_dtype)
-            dshift = sums[0].view(t_shape).to(t_dtype)
-        return dx, dscale, dshift
+        return _plane_affine_backward(ctx, gy, False)
 
 
 class InstanceNorm(torch.autograd.Function):

@@ -7,7 +7,6 @@ from __future__ import annotations
 
 import ctypes as C
 import os
-from typing import Optional
 
 import torch
 
@@ -34,21 +33,7 @@ def float_copy_is_channels_last(x: torch.Tensor, cfg, chan_perm) -> bool:
     return _F._nhwc_call(twin, cfg, chan_perm)
 
 
-def _require_f64(x, what: str):
-    if not isinstance(x, torch.Tensor):
-        raise TypeError(f"{what}: expected a tensor")
-    if not x.is_cuda:
-        raise _ffi.CnsnError(f"{what}: got a {x.device.type} tensor. This implementation runs on MI355X HIP device "
-                             "tensors only; there is no CPU path.")
-    if x.dtype != torch.float64:
-        raise TypeError(f"{what}: expected a float64 tensor, got {x.dtype}")
-    assert x.dim() == 4, "expected an (N, C, H, W) tensor"
-
-
-def _f64(t: torch.Tensor) -> torch.Tensor:
-    if t.dtype == torch.float64 and t.is_contiguous():
-        return t.detach() if t.requires_grad else t
-    return t.detach().to(torch.float64).contiguous()
+_F64 = (torch.float64,)
 
 
 def _scalars(cfg) -> _ffi.F64Scalars:
@@ -58,14 +43,7 @@ def _scalars(cfg) -> _ffi.F64Scalars:
 
 def _problem(x, cfg) -> _ffi.Problem:
     """cnsn_problem_t of a float64 call (its float scalar fields are not read: `_scalars`)"""
-    p = _ffi.Problem()
-    p.struct_bytes = C.sizeof(_ffi.Problem)
-    p.dtype = _ffi.CNSN_F64
-    p.N, p.C, p.H, p.W = (int(s) for s in x.shape)
-    p.cn_active = int(cfg.cn_active)
-    p.content_box = _ffi.box4(cfg.content_box)
-    p.style_box = _ffi.box4(cfg.style_box)
-    p.sn_active, p.sn_two, p.sn_training = int(cfg.sn_active), int(cfg.sn_two), int(cfg.sn_training)
+    p = _F._problem_shape(x, cfg, _ffi.CNSN_F64)
     p.layout = _ffi.LAYOUT_NCHW
     return p
 
@@ -79,35 +57,15 @@ def _sizes(prob):
     return lib.cnsn_saved_floats(C.byref(twin)), lib.cnsn_workspace_bytes_f64(C.byref(prob))
 
 
-class _GateBuffersF64:
-    """a gate's tensors as the float64 kernels take them + the cnsn_gate_f64_t that points at them.  A float64 module
-    (`SelfNorm.double()`) passes its parameters and buffers as they are; a float32 module passes double copies, and its
-    running statistics are copied back — rounded to float32 — after a training-mode launch."""
-
-    def __init__(self, w, gamma, beta, rm, rv, nbt, training):
-        self.w, self.gamma, self.beta = _f64(w), _f64(gamma), _f64(beta)
-        self.src_rm, self.src_rv, self.training = rm, rv, bool(training)
-        self.direct = all(t.dtype == torch.float64 and t.is_contiguous() for t in (rm, rv))
-        self.rm = rm.detach() if self.direct else _f64(rm)
-        self.rv = rv.detach() if self.direct else _f64(rv)
-        if nbt is not None and not (training and nbt.dtype == torch.int64 and nbt.is_cuda and nbt.numel() == 1):
-            if training:        # a counter the kernel cannot reach is counted here, as nn.BatchNorm1d.forward does
-                nbt.add_(1)
-            nbt = None
-        self.nbt = nbt if training else None
-        self.c = _ffi.GateF64(C.sizeof(_ffi.GateF64), 0, self.w.data_ptr(), self.gamma.data_ptr(), self.beta.data_ptr(),
-                              self.rm.data_ptr(), self.rv.data_ptr(), _F._ptr(self.nbt))
-
-    def write_back(self):
-        if self.training and not self.direct:
-            self.src_rm.copy_(self.rm)
-            self.src_rv.copy_(self.rv)
+def _gate(w, gamma, beta, rm, rv, nbt, training):
+    """a gate's tensors as the float64 kernels take them.  A float64 module (`SelfNorm.double()`) passes its parameters and
+    buffers as they are; a float32 module passes double copies, and its running statistics are copied back — rounded to
+    float32 — after a training-mode launch."""
+    return _F._GateBuffers(w, gamma, beta, rm, rv, nbt, training, torch.float64, _ffi.GateF64)
 
 
 def _gate_grad_views(c: int, dev):
-    flat = torch.empty(4 * c, dtype=torch.float64, device=dev)
-    rows = [flat[:2 * c].view(c, 1, 2), *flat[2 * c:].view(2, c).unbind(0)]
-    return rows, _ffi.GateGradF64(C.sizeof(_ffi.GateGradF64), 0, rows[0].data_ptr(), rows[1].data_ptr(), rows[2].data_ptr())
+    return _F._gate_grad_views(c, dev, 0, torch.float64, _ffi.GateGradF64)
 
 
 class FusedCNSNF64(torch.autograd.Function):
@@ -117,7 +75,7 @@ class FusedCNSNF64(torch.autograd.Function):
     @_F._on_device_of
     def forward(ctx, x, cfg, perm, chan_perm, g_w, g_gamma, g_beta, g_rm, g_rv, f_w, f_gamma, f_beta, f_rm, f_rv,
                 g_nbt=None, f_nbt=None):
-        _require_f64(x, "cnsn_forward_f64")
+        _F._require_device(x, "cnsn_forward_f64", _F64)
         assert not cfg.has_epilogue, "the float64 path has no epilogue (CNSN.forward_block composes it)"
         lib = _ffi.lib()
         x = _F._dense(x)                         # NCHW copy of anything else, as the reference's .contiguous() (cnsn.py:14)
@@ -128,8 +86,8 @@ class FusedCNSNF64(torch.autograd.Function):
             chan_perm = _F._h2d.to_device(chan_perm, dev) if chan_perm is not None else None
         else:
             perm = chan_perm = None
-        gate_g = _GateBuffersF64(g_w, g_gamma, g_beta, g_rm, g_rv, g_nbt, cfg.sn_training) if cfg.sn_active else None
-        gate_f = _GateBuffersF64(f_w, f_gamma, f_beta, f_rm, f_rv, f_nbt, cfg.sn_training) \
+        gate_g = _gate(g_w, g_gamma, g_beta, g_rm, g_rv, g_nbt, cfg.sn_training) if cfg.sn_active else None
+        gate_f = _gate(f_w, f_gamma, f_beta, f_rm, f_rv, f_nbt, cfg.sn_training) \
             if (cfg.sn_active and cfg.sn_two) else None
         y = torch.empty_like(x)
         need_bwd = any(ctx.needs_input_grad)
@@ -196,29 +154,12 @@ class PlaneStatsF64(torch.autograd.Function):
     @staticmethod
     @_F._on_device_of
     def forward(ctx, x, eps, box):
-        _require_f64(x, "calc_ins_mean_std")
-        x = _F._dense(x)
-        n, c, h, w = _F._dims(x)
-        ms = torch.empty(2, n * c, dtype=torch.float64, device=x.device)
-        st = _ffi.lib().cnsn_plane_stats_f64(_F._ptr(x), n, c, h, w, _ffi.box4(box) if box else None, float(eps), _F._ptr(ms),
-                                             _F._stream(x))
-        _ffi.check(st, "cnsn_plane_stats_f64")
-        ctx.box = box
-        ctx.save_for_backward(x, ms)
-        return ms[0].view(n, c, 1, 1), ms[1].view(n, c, 1, 1)
+        return _F._plane_stats_forward(ctx, x, eps, box, True)
 
     @staticmethod
     @_F._on_device_of
     def backward(ctx, gmean, gstd):
-        x, ms = ctx.saved_tensors
-        n, c, h, w = _F._dims(x)
-        gm, gs = _f64(gmean).reshape(-1), _f64(gstd).reshape(-1)
-        dx = torch.empty_like(x)
-        st = _ffi.lib().cnsn_plane_stats_backward_f64(_F._ptr(x), n, c, h, w, _ffi.box4(ctx.box) if ctx.box else None,
-                                                      _F._ptr(ms[0]), _F._ptr(ms[1]), _F._ptr(gm), _F._ptr(gs), _F._ptr(dx),
-                                                      _F._stream(x))
-        _ffi.check(st, "cnsn_plane_stats_backward_f64")
-        return dx, None, None
+        return _F._plane_stats_backward(ctx, gmean, gstd, True), None, None
 
 
 class PlaneAffineF64(torch.autograd.Function):
@@ -227,36 +168,9 @@ class PlaneAffineF64(torch.autograd.Function):
     @staticmethod
     @_F._on_device_of
     def forward(ctx, x, scale, shift):
-        _require_f64(x, "plane_affine")
-        x = _F._dense(x)
-        n, c, h, w = _F._dims(x)
-        sc, sh = _f64(scale).reshape(-1), _f64(shift).reshape(-1)
-        assert sc.numel() == n * c and sh.numel() == n * c, "one scale and one shift per plane"
-        y = torch.empty_like(x)
-        st = _ffi.lib().cnsn_plane_affine_f64(_F._ptr(x), n, c, h, w, _F._ptr(sc), _F._ptr(sh), _F._ptr(y), _F._stream(x))
-        _ffi.check(st, "cnsn_plane_affine_f64")
-        ctx.save_for_backward(x, sc)
-        ctx.meta = (scale.shape, scale.dtype, shift.shape, shift.dtype)
-        return y
+        return _F._plane_affine_forward(ctx, x, scale, shift, True)
 
     @staticmethod
     @_F._on_device_of
     def backward(ctx, gy):
-        lib = _ffi.lib()
-        x, sc = ctx.saved_tensors
-        n, c, h, w = _F._dims(x)
-        gy = _F._grad_like(gy, x, False)
-        dx = dscale = dshift = None
-        if ctx.needs_input_grad[0]:
-            dx = torch.empty_like(x)
-            zero = torch.zeros_like(sc)
-            st = lib.cnsn_plane_affine_f64(_F._ptr(gy), n, c, h, w, _F._ptr(sc), _F._ptr(zero), _F._ptr(dx), _F._stream(x))
-            _ffi.check(st, "cnsn_plane_affine_f64(backward)")
-        if ctx.needs_input_grad[1] or ctx.needs_input_grad[2]:
-            sums = torch.empty(2, n * c, dtype=torch.float64, device=x.device)
-            st = lib.cnsn_plane_dot_f64(_F._ptr(gy), _F._ptr(x), n, c, h, w, _F._ptr(sums), _F._stream(x))
-            _ffi.check(st, "cnsn_plane_dot_f64")
-            s_shape, s_dtype, t_shape, t_dtype = ctx.meta
-            dscale = sums[1].view(s_shape).to(s_dtype)
-            dshift = sums[0].view(t_shape).to(t_dtype)
-        return dx, dscale, dshift
+        return _F._plane_affine_backward(ctx, gy, True)

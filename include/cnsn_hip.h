@@ -626,7 +626,8 @@ int cnsn_jsd(const void* logits_clean, const void* logits_aug1, const void* logi
 
 /* ---- float64 (additive; the ABI number stays) -------------------------------------------------------------------------------
  * The op and the per-plane primitives for `double` tensors: elements, plane statistics, every side array, the gate's
- * parameters, running statistics and parameter gradients are all float64, and so is the arithmetic (csrc/cnsn_f64_kernels.h).
+ * parameters, running statistics and parameter gradients are all float64, and so is the arithmetic (the `double` instantiations of
+ * csrc/cnsn_stream_kernels.h and csrc/cnsn_mid_kernels.h).
  * What it is for: a model moved to .double() to chase a numerical problem, torch.autograd.gradcheck, and holding the backward
  * algebra to 1e-10 on the device.  Always the two-pass streaming kernels (cnsn_problem_t.strategy, context and perm_host are
  * ignored): plain launches, no persistent grid, capturable into a graph.  Same rules as the float entry points: caller-owned

@@ -218,7 +218,7 @@ def test_float_copy_route_misses_the_bar(kind, is_two, monkeypatch):
 
 
 # ---- 3. geometry: every instantiation and tail of the tensor passes.  Lanes per plane by the number of 16-byte vectors
-# (csrc/cnsn_f64.hip::pick_shape_f64): <= 32 -> 16, <= 4096 -> 64, above -> the whole block; VEC = 2 on even planes (rows, with boxes)
+# (csrc/cnsn_host_plan.h::pick_shape): <= 32 -> 16, <= 4096 -> 64, above -> the whole block; VEC = 2 on even planes (rows, with boxes)
 def geometry_case(shape, kind, is_two, training, cbox=None, sbox=None, lam=None, chan=False):
     seed = seed_of(shape, kind, is_two, training, cbox, sbox, lam, chan)
     gen = torch.Generator().manual_seed(seed)
@@ -243,6 +243,13 @@ def geometry_case(shape, kind, is_two, training, cbox=None, sbox=None, lam=None,
 def test_unboxed_geometry(shape):
     geometry_case(shape, "cnsn", True, True, chan=shape[1] > 1)
     geometry_case(shape, "sn", False, False)
+
+
+def test_batch_beyond_one_workgroup_step():
+    """N = 257: the smallest batch at which a thread of the double mid kernels (one workgroup of 256 threads per channel)
+    takes a second step through its instances"""
+    geometry_case((257, 2, 2, 3), "cnsn", True, True, chan=True)
+    geometry_case((257, 2, 2, 3), "sn", False, True)
 
 
 def test_single_instance():
