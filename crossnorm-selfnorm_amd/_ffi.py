@@ -156,6 +156,13 @@ SIGNATURES = {
                                       C.c_void_p]),
     "cnsn_backward_bn_act": (C.c_int, [C.POINTER(BnAct), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
                                        C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]),
+    "cnsn_bn_act_nchw_plan": (C.c_int, [C.POINTER(BnAct), C.c_int, C.c_int]),
+    "cnsn_bn_act_nchw_workspace_bytes": (C.c_size_t, [C.POINTER(BnAct)]),
+    "cnsn_bn_act_nchw_geometry": (C.c_int, [C.POINTER(BnAct), C.c_int, C.POINTER(C.c_int32)]),
+    "cnsn_forward_bn_act_nchw": (C.c_int, [C.POINTER(BnAct), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                           C.c_size_t, C.c_void_p]),
+    "cnsn_backward_bn_act_nchw": (C.c_int, [C.POINTER(BnAct), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                            C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]),
     "cnsn_jsd_workspace_bytes": (C.c_size_t, [C.c_int]),
     "cnsn_jsd": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p,
                            C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]),

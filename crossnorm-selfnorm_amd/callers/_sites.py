@@ -14,6 +14,9 @@ FUSE_TAIL = FUSE_BLOCK and os.environ.get("CNSN_FUSE_TAIL", "1") != "0"
 # `relu(bn(x))` and the plain block end `relu(bn3(h) + skip)` through this library's single launch on channels-last tensors
 # (callers/bn_act.py, cnsn_forward_bn_act).  CNSN_BN_ACT=0 (or setting this to False) keeps nn.BatchNorm2d and the ReLU.
 FUSE_BN_ACT = os.environ.get("CNSN_BN_ACT", "1") != "0"
+# ... and on dense NCHW tensors through the library's two plain launches per direction (functional.BatchNormActNCHW,
+# cnsn_forward_bn_act_nchw).  Off unless CNSN_BN_ACT_NCHW=1 (or this is set to True): NCHW calls keep nn.BatchNorm2d and the ReLU.
+FUSE_BN_ACT_NCHW = os.environ.get("CNSN_BN_ACT_NCHW", "0") == "1"
 
 
 def residual_sum(cnsn, pos, residual, skip, relu, skip_first=False):

@@ -11,6 +11,13 @@ import torch.nn.functional as F
 
 from . import _sites
 from ._sites import CrossNormSites, make_cnsn, residual_sum
+from .bn_act import bn_act
+
+
+def _bn_relu(bn, relu, x):
+    """`relu(bn(x))` of two modules the network owns: through `bn_act` (one call of this library where it takes the tensor)
+    with `_sites.FUSE_BN_ACT_NCHW` on, the two modules as they are otherwise"""
+    return bn_act(bn, x) if _sites.FUSE_BN_ACT_NCHW else relu(bn(x))
 
 
 class _Block(nn.Module):
@@ -41,11 +48,11 @@ class _Block(nn.Module):
         returns `(y, z)` with z = relu(next_bn(y)) from its own CNSN launch (`CNSN.forward_block_bn`), y = None when
         `want_y` is False (the next block only consumes z: its widths differ, wideresnet_cnsn.py:69-70)."""
         if not self.same_width:
-            x = pre if pre is not None else self.relu1(self.bn1(x))
+            x = pre if pre is not None else _bn_relu(self.bn1, self.relu1, x)
         h = self.cnsn(x) if self.pos == "pre" else x
         if self.same_width:
-            h = pre if (pre is not None and self.pos != "pre") else self.relu1(self.bn1(h))
-        h = self.relu2(self.bn2(self.conv1(h)))
+            h = pre if (pre is not None and self.pos != "pre") else _bn_relu(self.bn1, self.relu1, h)
+        h = _bn_relu(self.bn2, self.relu2, self.conv1(h))
         if self.drop_rate > 0:
             h = F.dropout(h, p=self.drop_rate, training=self.training)
         h = self.conv2(h)
@@ -100,7 +107,7 @@ class WideResNetCNSN(nn.Module, CrossNormSites):
             self._enable_cross_norm()
         if not (_sites.FUSE_TAIL and self.pos == "post"):
             h = self.block3(self.block2(self.block1(self.conv1(x))))
-            h = F.avg_pool2d(self.relu(self.bn1(h)), 8)
+            h = F.avg_pool2d(_bn_relu(self.bn1, self.relu, h), 8)
             return self.fc(h.view(h.size(0), -1))
         # every block hands `relu(bn1(.))` of the block that follows (:76-77 / :69-70; after the last one: :222) out of
         # its own CNSN launch, next to its output; module ownership — and with it every state_dict key — is unchanged
@@ -114,7 +121,7 @@ class WideResNetCNSN(nn.Module, CrossNormSites):
             if z is None:                     # (no tail offered at this site this step: the next block does it itself)
                 h, pre = y, None
                 if last:
-                    z = self.relu(self.bn1(y))
+                    z = _bn_relu(self.bn1, self.relu, y)
             else:
                 h, pre = (y if y is not None else z), z   # (y None: the next block never looks at h itself)
         return self.fc(F.avg_pool2d(z, 8).view(z.size(0), -1))

@@ -1224,6 +1224,93 @@ class BatchNormAct(torch.autograd.Function):
             return dx, (da if ctx.has_addend else None), dw, db, None, None, None, None, None, None, None
 
 
+# ------------------------------------------------------------------------------------------------
+# BatchNorm2d (+ add) + ReLU on NCHW tensors: the same function in TWO ordinary launches per direction (cnsn_forward_bn_act_nchw /
+# cnsn_backward_bn_act_nchw, csrc/cnsn_nchw_bn_kernels.h) — no persistent grid, no barrier, no context, nothing to poll
+# ------------------------------------------------------------------------------------------------
+_bn_act_nchw_plan_cache = _plan_cache()
+
+
+def bn_act_nchw_plan(x: torch.Tensor, relu: bool = True, has_addend: bool = False, training: bool = True) -> bool:
+    """True when the library's two plain launches evaluate `act(BatchNorm2d(x) [+ addend])` for this tensor
+    (cnsn_bn_act_nchw_plan): a dense NCHW HIP tensor, fp32 / bf16 / f16, any C, H, W, fewer than 2^31 elements; training mode
+    (both directions) with N*H*W >= 2, eval mode forward only.  A pure function of the tensor's shape and dtype: no switch and no
+    health enters it.  Remembered per (shape, dtype, mode)."""
+    if not x.is_cuda or x.dim() != 4 or x.dtype not in _DTYPES or not x.is_contiguous():
+        return False
+
+    def ask():
+        d = _bn_act_desc(x, relu, has_addend, training=training)
+        return all(_ffi.lib().cnsn_bn_act_nchw_plan(C.byref(d), int(has_addend), back) == 1 for back in ((0, 1) if training else (0,)))
+    return _remembered(_bn_act_nchw_plan_cache, (tuple(x.shape), x.dtype, bool(training)), ask)
+
+
+def bn_act_nchw_geometry(x: torch.Tensor, training: bool = True, backward: bool = False):
+    """(tiles per channel, instances per tile, elements per plane range, threads per workgroup) of the launches on `x`
+    (cnsn_bn_act_nchw_geometry)"""
+    d = _bn_act_desc(x, True, False, training=training)
+    out = (C.c_int32 * 4)()
+    _ffi.check(_ffi.lib().cnsn_bn_act_nchw_geometry(C.byref(d), int(backward), out), "cnsn_bn_act_nchw_geometry")
+    return tuple(out)
+
+
+class BatchNormActNCHW(torch.autograd.Function):
+    """y = act(BatchNorm2d(x) [+ addend]) on a dense NCHW tensor, two plain launches per direction in training mode (the tiles'
+    partial sums, then every tile with its channel's statistics), one in eval mode.  Saves x, the addend when the ReLU follows
+    it, and 2*C floats (mean, rstd) — never y.  The launches can be recorded under stream capture.  The caller resolves
+    BatchNorm2d's per-call book-keeping, as for BatchNormAct."""
+
+    @staticmethod
+    def forward(ctx, x, addend, bn_w, bn_b, bn_rm, bn_rv, relu, training, bn_eps, bn_momentum, bn_nbt=None):
+        _require_device(x, "cnsn_forward_bn_act_nchw")
+        with torch.cuda.device(x.device):
+            lib = _ffi.lib()
+            x = _dense(x)
+            addend = None if addend is None else _addend_like(x, addend, "cnsn_forward_bn_act_nchw", _dense)
+            dev = x.device
+            bn = _Bn2dBuffers(bn_w, bn_b, bn_rm, bn_rv, bn_eps, bn_momentum, bn_nbt, training)
+            d = _bn_act_desc(x, relu, addend is not None, bn.c, training)
+            need_bwd = bool(training) and any(ctx.needs_input_grad)    # (eval: forward only, the output carries no gradient)
+            saved = torch.empty(lib.cnsn_bn_act_saved_floats(C.byref(d)), dtype=torch.float32, device=dev) if need_bwd else None
+            ws_bytes = lib.cnsn_bn_act_nchw_workspace_bytes(C.byref(d))
+            ws = _workspace(ws_bytes, dev)
+            y = _out_like(x)
+            st = lib.cnsn_forward_bn_act_nchw(C.byref(d), _ptr(x), _ptr(addend), _ptr(y), _ptr(saved), _ptr(ws), ws_bytes, _stream(x))
+            _ffi.check(st, "cnsn_forward_bn_act_nchw")
+            bn.write_back()
+            if not training:
+                ctx.mark_non_differentiable(y)
+            if need_bwd:
+                ctx.desc, ctx.keep = d, bn                         # (the descriptor points at the float32 parameters)
+                ctx.has_addend, ctx.relu = addend is not None, bool(relu)
+                ctx.param_dtypes = (bn_w.dtype, bn_b.dtype)
+                ctx.save_for_backward(x, addend if relu else None, saved)
+            return y
+
+    @staticmethod
+    def backward(ctx, gy):
+        x, addend, saved = ctx.saved_tensors
+        with torch.cuda.device(x.device):
+            lib = _ffi.lib()
+            d = ctx.desc
+            dev = x.device
+            c = int(x.shape[1])
+            gy = _grad_like(gy, x, False)
+            dx = _out_like(x)
+            da = _out_like(x) if addend is not None else None    # (ReLU behind the addend: the masked gradient)
+            dw, db = torch.empty(2 * c, dtype=torch.float32, device=dev).view(2, c).unbind(0)
+            ws_bytes = lib.cnsn_bn_act_nchw_workspace_bytes(C.byref(d))
+            ws = _workspace(ws_bytes, dev)
+            st = lib.cnsn_backward_bn_act_nchw(C.byref(d), _ptr(gy), _ptr(x), _ptr(addend), _ptr(saved), _ptr(dx), _ptr(da),
+                                               _ptr(dw), _ptr(db), _ptr(ws), ws_bytes, _stream(x))
+            _ffi.check(st, "cnsn_backward_bn_act_nchw")
+            if ctx.has_addend and da is None:
+                da = gy                                          # (no ReLU: the addend's gradient is grad_y itself)
+            dw, db = _cast_grads((dw, db), ctx.param_dtypes)
+            #       x   addend                          w   b   rm    rv    relu  train eps   mom   nbt
+            return dx, (da if ctx.has_addend else None), dw, db, None, None, None, None, None, None, None
+
+
 class JsdConsistency(torch.autograd.Function):
     """Jensen-Shannon consistency of three (B, K) logit tensors — cnsn_jsd: loss and gradient in one launch
     (reference imagenet.py:367-381, cifar.py:173-186)."""

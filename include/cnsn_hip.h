@@ -460,6 +460,42 @@ int cnsn_backward_bn_act(const cnsn_bn_act_t* desc, const void* grad_y, const vo
                          void* grad_x, void* grad_addend, float* d_weight, float* d_bias, void* workspace, size_t workspace_bytes,
                          void* stream);
 
+/* ---- BatchNorm2d (+ add) + ReLU on NCHW tensors (ABI 9, added in round 12: purely additive, the number stays) -----------------
+ * The same function, y = act( BatchNorm2d(x) [+ addend] ), the same descriptor (cnsn_bn_act_t, unchanged; `context` is ignored)
+ * and the same argument lists as the channels-last entry points above, for a dense NCHW tensor: a channel is N planes of
+ * P = H*W contiguous elements at stride C*P — csrc/cnsn_nchw_bn_kernels.h.
+ *   training: TWO ordinary launches per direction — no persistent grid, no grid barrier, no wait, no context, nothing to poll;
+ *     they can be recorded under stream capture.  A tile is one channel x a range of instances x a range of the plane
+ *     (cnsn_bn_act_nchw_geometry).  Launch 1 writes every tile's two partial sums (forward: sum(x - s), sum((x - s)^2) about
+ *     s = the channel's first element; backward: sum G', sum G'*(x - mean), G' = grad_y masked by the ReLU) to
+ *     workspace[c][tile]; launch 2 has every workgroup add ITS channel's partials in double in one fixed order — all tiles of
+ *     a channel hold bit-identical mean / rstd — and stream its tile.  Tile 0 of a channel writes `saved`, running_mean /
+ *     running_var (unbiased, `momentum`), d_weight and d_bias; channel 0 counts num_batches_tracked.  No atomics: two calls on
+ *     the same input are bit-identical.  Tensor passes 3 + 5, values rounded where the un-fused sequence rounds them and the
+ *     ReLU mask recomputed with the forward's own expression, as above.
+ *   eval: the running statistics, one plain launch, forward only.
+ *   - fp32 / bf16 / f16 activations, fp32 parameters and statistics; any C >= 1, any H, W; training: N*H*W >= 2.  16-byte
+ *     accesses on the aligned body of every plane range, scalar head and tail where H*W*sizeof(T) is no multiple of 16.
+ *   - index range: N*C*H*W < 2^31 elements (offsets are 64-bit; the bound keeps every count and the grid, C * tiles, in 32 bits).
+ *   - ineligible — training with N*H*W < 2, a base pointer that is not 16-byte aligned, sizes beyond the index range, eval with
+ *     backward = 1 — returns CNSN_E_UNSUPPORTED and launches nothing.  No switch, no health: everything here but the two
+ *     launches is a pure function of the descriptor.
+ *   - `saved`: cnsn_bn_act_saved_floats() (2*C floats: mean, rstd).  workspace: cnsn_bn_act_nchw_workspace_bytes(), either
+ *     direction (at least C * tiles * 2 floats).
+ *   - backward: grad_x, d_weight, d_bias (either may be NULL) are written, not accumulated; grad_addend as above. */
+/* 1 when the launches take a call with this descriptor (aligned pointers assumed), 0 when not, < 0 argument error */
+int cnsn_bn_act_nchw_plan(const cnsn_bn_act_t* desc, int has_addend, int backward);
+size_t cnsn_bn_act_nchw_workspace_bytes(const cnsn_bn_act_t* desc);
+/* out = { tiles per channel, instances per tile, elements per plane range, threads per workgroup }: tile t of a channel takes
+ * instances [ig*out[1], ..) and plane elements [s*out[2], ..) with ig = t / S, s = t % S, S = ceil(H*W / out[2]), both ranges
+ * cut at N and H*W.  One geometry for both directions (`backward` is checked like the plan's).  CNSN_OK or the plan's refusal. */
+int cnsn_bn_act_nchw_geometry(const cnsn_bn_act_t* desc, int backward, int32_t out[4]);
+int cnsn_forward_bn_act_nchw(const cnsn_bn_act_t* desc, const void* x, const void* addend, void* y, float* saved, void* workspace,
+                             size_t workspace_bytes, void* stream);
+int cnsn_backward_bn_act_nchw(const cnsn_bn_act_t* desc, const void* grad_y, const void* x, const void* addend,
+                              const float* saved, void* grad_x, void* grad_addend, float* d_weight, float* d_bias, void* workspace,
+                              size_t workspace_bytes, void* stream);
+
 /* ---- persistent exchange context of the cluster-resident strategy --------------------------------
  * The resident kernels hand per-plane scalars from workgroup to workgroup through device memory.  Through the
  * per-call `workspace` (contents unknown) that memory has to be filled with an 'empty' pattern by a launch of its own
